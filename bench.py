@@ -8,6 +8,12 @@ Workload: BASELINE.json's metric config — 1M synthetic "trained-like" Gaussian
 camera with the Lego field of view on a radius-4 orbit, 1920x1080, SH degree 3, default 3dgut.yaml flags.
 Each rank renders its own view (weak scaling); for N>1 the packed Gaussian gradients are sum-all-reduced
 over RCCL every step (the path's one exchange step).
+
+A plain run sets up, warms up, times `--steps` steps and prints the line (metric, value, unit, ms_per_step, ...); on the 3DGUT path
+the warm-up is followed by as many untimed steps as `--full` spends on its stage breakdown, so both start timing from the same state.
+Everything else the benchmark measures - the stage breakdown and rooflines (instrumented frames and an all-stage pass of their own),
+the CPU baseline, the training surrogate and the secondary workloads of the default line - runs only with `--full`.
+`--dump-outputs DIR` writes what the timed path returned in its last step (`dump_outputs`).
 """
 import argparse
 import ctypes as C
@@ -48,6 +54,37 @@ WORKLOADS = {
     "c3_grt_sphere_1m_800": (1_000_000, 800, 800, 0.01),     # OptiX's built-in spheres: entry and exit of every enclosing sphere, each a proxy of its own
 }
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s HBM3E peak
+DUMP_BYTES = 60 << 20  # --dump-outputs: all arrays together (within 64 MB with the .npy headers)
+GRAD_NAMES = ("positions", "rotation", "scale", "density", "features")   # SimpleGaussians.parameters(), in order
+
+
+def caller_outputs(out, g=None):
+    """What a caller of the timed path receives from one step: the render's tensors and, after the backward, the Gaussians' gradients."""
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    if g is not None:
+        for name, p in zip(GRAD_NAMES, g.parameters()):
+            if p.grad is not None:
+                arrays["grad_" + name] = p.grad
+    return arrays
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: one float32 DIR/<name>.npy per array.  An array is read as rows (pixels or particles: every axis but the last);
+    where all of them together would pass DUMP_BYTES, every array keeps the same number of rows, a fixed sample (seed 0, sorted) that is
+    the same for every array of that many rows and for every run, so that two builds run with the same arguments compare file by file."""
+    mats = {k: v.detach().reshape(-1, v.shape[-1] if v.dim() > 1 else 1) for k, v in arrays.items()}
+    rows = DUMP_BYTES // (4 * max(1, sum(m.shape[1] for m in mats.values())))
+    os.makedirs(path, exist_ok=True)
+    samples = {}
+    for k, v in arrays.items():
+        m = mats[k]
+        if m.shape[0] > rows:
+            if m.shape[0] not in samples:
+                samples[m.shape[0]] = torch.as_tensor(np.sort(np.random.default_rng(0).choice(m.shape[0], rows, replace=False)), device=m.device)
+            a = m[samples[m.shape[0]]]
+        else:
+            a = v.detach()
+        np.save(os.path.join(path, f"{k}.npy"), a.float().cpu().numpy())
 
 
 def byte_model(N, Nv, I, P, tile_bits, sph_coeffs=16):
@@ -225,14 +262,15 @@ def bench_grt(args, world, rank, dev, dist, n, W, H, ms, name=None, emit=True):
         torch.autograd.backward([fd], [g_fd])
         if world > 1:
             exch.reduce()
+        return out
 
     for _ in range(args.warmup):
         step()
     tracer.timings
     torch.cuda.synchronize()
-    # one instrumented frame (outside the timed region): the traversal's work counters for the byte model
+    # --full: one instrumented frame (outside the timed region): the traversal's work counters for the byte model
     work = None
-    if rank == 0:
+    if rank == 0 and args.full:
         os.environ["GRUT_GRT_COUNT"] = "1"
         step()
         torch.cuda.synchronize()
@@ -248,8 +286,9 @@ def bench_grt(args, world, rank, dev, dist, n, W, H, ms, name=None, emit=True):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    out = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -262,14 +301,20 @@ def bench_grt(args, world, rank, dev, dist, n, W, H, ms, name=None, emit=True):
     stages = tracer.timings
     result = None
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, caller_outputs(out, g))
         P = W * H
         result = {
             "metric": "train rays/sec (3DGRT forward+backward, primary rays; software BVH + per-frame packet lists)", "value": world * P * args.steps / dt,
             "unit": "rays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"3DGRT BVH build + fwd + bwd, {n} Gaussians (cloud B trained-like, seed 42), {W}x{H}, one view per GPU, "
-                                   f"SH degree 3, k = 16 hits per trace", "name": name, "parallelism": f"view-dp{world}"},
-            "roofline": grt_roofline(work, P, stages), "roofline_backward": grt_backward_roofline(work, P, stages, {"words": work.get("bwd_atomic_words"), "instructions": work.get("bwd_atomic_instructions")} if work else None), "stages_ms": stages, "work": work}
+                                   f"SH degree 3, k = 16 hits per trace", "name": name, "parallelism": f"view-dp{world}"}}
+        if args.full:
+            atomics = {"words": work.get("bwd_atomic_words"), "instructions": work.get("bwd_atomic_instructions")} if work else None
+            result.update(roofline=grt_roofline(work, P, stages), roofline_backward=grt_backward_roofline(work, P, stages, atomics), stages_ms=stages, work=work)
+        else:
+            result["stages_ms"] = stages
         if emit:
             print(json.dumps(result), flush=True)
     if world > 1 and emit:
@@ -338,6 +383,8 @@ def bench_hybrid(args, dev, n, W, H, ms, emit=True):
         out = tr.render_playground(*args_t, frame_id=k, **kw)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, caller_outputs(out))
     b = out["mirror_bounces"]
     result = {"metric": "rays/sec (hybrid mesh + Gaussian path tracing, forward)", "value": W * H * args.steps / dt, "unit": "rays/s",
               "ms_per_step": dt / args.steps * 1e3, "steps": args.steps, "warmup": args.warmup, "n_gpus": 1, "higher_is_better": True, "dtype": "f32",
@@ -373,16 +420,20 @@ def bench_nht(args, dev, n, W, H, ms, emit=True):
         g.zero_grad()
         out = tracer.render(g, batch, train=True)
         torch.autograd.backward([out["pred_features"], out["pred_opacity"]], [g_feat, g_opa])
+        return out
 
     for _ in range(args.warmup):
         step()
     tracer.timings
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    out = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, caller_outputs(out, g))
     st = tracer.tracer_wrapper.stats()
     result = {"metric": "train rays/sec (3DGUT, neural harmonic features, forward+backward)", "value": W * H * args.steps / dt, "unit": "rays/s",
               "ms_per_step": dt / args.steps * 1e3, "steps": args.steps, "warmup": args.warmup, "n_gpus": 1, "higher_is_better": True, "dtype": "f32",
@@ -446,10 +497,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="c4_1m_1080p", choices=list(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short 3DGRT (BASELINE config 3) measurement appended to the default line")
+    ap.add_argument("--full", action="store_true", help="also measure the stage breakdown and rooflines, the CPU baseline, the training "
+                                                         "surrogate and the secondary workloads of the default line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path returned in its last step to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary measurements appended to the default line")
     ap.add_argument("--k-buffer", type=int, default=0, help="3DGUT sorted mode (render.splat.k_buffer_size); 0 = the headline configuration")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -538,6 +594,7 @@ def main():
         torch.autograd.backward([out["pred_features"], out["pred_opacity"]], [g_rgb, g_opa])
         if exch is not None:  # in-place all-reduce of the Gaussian gradients ([N,59] fp32 in five tensors)
             exch.reduce()
+        return out
 
     untouched = None
     exchange_fallback = None
@@ -564,33 +621,40 @@ def main():
             if untouched > 0.25:
                 exchange_kind = "visible"
                 tracer.gradient_exchange = dp.VisibleRowsExchange(average=False, timed=True)
-    # one instrumented frame outside the timed region: the sweeps count the tile entries they evaluate / accept (roofline.touched_bytes)
-    abi.check(nat.lib.gut_profile_enable(nat.handle, 2), "gut_profile_enable")
-    step()
-    torch.cuda.synchronize()
-    work = nat.stats()
-    abi.check(nat.lib.gut_profile_enable(nat.handle, 1), "gut_profile_enable")
-    step()   # back on the uninstrumented kernels before timing
-    abi.check(nat.lib.gut_profile_read(nat.handle, (C.c_float * len(abi.GUT_STAGES))()), "gut_profile_read")   # drop the two frames' stage times
-    # Stage breakdown OUTSIDE the timed region: an event pair around every stage leaves ~10 us of idle stream at each of the eight
-    # stage boundaries (profiles/r02m_timeline.txt), 3.5 % of the step, which the product's default configuration
-    # (enable_kernel_timings off, like the reference's) does not pay.  The timed region below keeps the events of the DOMINANT kernel
-    # only: its average launch duration there is what `roofline` prices.
-    for _ in range(min(args.steps, 20)):
+    if args.full:
+        # one instrumented frame outside the timed region: the sweeps count the tile entries they evaluate / accept (roofline.touched_bytes)
+        abi.check(nat.lib.gut_profile_enable(nat.handle, 2), "gut_profile_enable")
         step()
-    stage_all = (C.c_float * len(abi.GUT_STAGES))()
-    abi.check(nat.lib.gut_profile_read(nat.handle, stage_all), "gut_profile_read")
-    dom_index = max(range(len(abi.GUT_STAGES)), key=lambda i: stage_all[i])
-    abi.check(nat.lib.gut_profile_select(nat.handle, 1 << dom_index), "gut_profile_select")
-    step()
-    abi.check(nat.lib.gut_profile_read(nat.handle, (C.c_float * len(abi.GUT_STAGES))()), "gut_profile_read")
+        torch.cuda.synchronize()
+        work = nat.stats()
+        abi.check(nat.lib.gut_profile_enable(nat.handle, 1), "gut_profile_enable")
+        step()   # back on the uninstrumented kernels before timing
+        abi.check(nat.lib.gut_profile_read(nat.handle, (C.c_float * len(abi.GUT_STAGES))()), "gut_profile_read")   # drop the two frames' stage times
+        # Stage breakdown OUTSIDE the timed region: an event pair around every stage leaves ~10 us of idle stream at each of the eight
+        # stage boundaries (profiles/r02m_timeline.txt), 3.5 % of the step, which the product's default configuration
+        # (enable_kernel_timings off, like the reference's) does not pay.  The timed region below keeps the events of the DOMINANT kernel
+        # only: its average launch duration there is what `roofline` prices.
+        for _ in range(min(args.steps, 20)):
+            step()
+        stage_all = (C.c_float * len(abi.GUT_STAGES))()
+        abi.check(nat.lib.gut_profile_read(nat.handle, stage_all), "gut_profile_read")
+        dom_index = max(range(len(abi.GUT_STAGES)), key=lambda i: stage_all[i])
+        abi.check(nat.lib.gut_profile_select(nat.handle, 1 << dom_index), "gut_profile_select")
+        step()
+        abi.check(nat.lib.gut_profile_read(nat.handle, (C.c_float * len(abi.GUT_STAGES))()), "gut_profile_read")
+    else:
+        # as many steps as the branch above runs before the timed region, without events or counters: the timed region starts from
+        # the same settled GPU in both modes (after the warm-up alone a step still runs ~1 % slower, ~5 % after a single one)
+        for _ in range(min(args.steps, 20) + 3):
+            step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    out = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -601,8 +665,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
-    stage_ms = (C.c_float * len(abi.GUT_STAGES))()
-    abi.check(nat.lib.gut_profile_read(nat.handle, stage_ms), "gut_profile_read")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, caller_outputs(out, g))
+    out = None
+    if args.full:
+        stage_ms = (C.c_float * len(abi.GUT_STAGES))()
+        abi.check(nat.lib.gut_profile_read(nat.handle, stage_ms), "gut_profile_read")
     st = nat.stats()
     exchange = None
     if world > 1:   # device time of the exchange step: every rank's average, the slowest reported
@@ -619,21 +687,6 @@ def main():
             exchange["fallback"] = exchange_fallback
     if rank == 0:
         P = W * H
-        # every stage from the all-stage pass; the dominant kernel from the timed region itself
-        stages = {k: float(stage_all[i]) for i, k in enumerate(abi.GUT_STAGES)}
-        stages[abi.GUT_STAGES[dom_index]] = float(stage_ms[dom_index])
-        model = byte_model(int(st.num_particles), int(st.num_visible), int(st.num_intersections), P, int(st.key_bits))
-        dom = max(stages, key=lambda k: stages[k])
-        achieved = model[dom] / (stages[dom] * 1e-3) / 1e9
-        traffic = None
-        pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(pmc):
-            try:
-                traffic = json.load(open(pmc)).get(args.workload, {}).get(dom)
-            except Exception:
-                traffic = None
-        touched = touched_bytes(dom, work, P, int(st.num_intersections))
-        total_bytes = sum(model.values())
         result = {
             "metric": "train rays/sec (3DGUT forward+backward, primary rays)",
             "value": world * P * args.steps / dt,
@@ -653,35 +706,53 @@ def main():
                                                                   "visible": " + OR-reduced row masks, then RCCL all-reduce / all-gather of the touched rows only",
                                                                   "sharded": " + RCCL reduce-scatter [N,12] + all-to-all of view factors + all-gather of the rebuilt shards",
                                                                   "none": ""}.get(exchange_kind, " + RCCL grad all-reduce [N,59]"))},
-            # `achieved` / `frac`: bytes the kernel can actually touch (evaluated entries, counted on the device) / its duration.
-            # `model_*`: SURVEY §8d's per-entry byte model applied to ALL I tile entries — an upper bound that charges the 88 % of the
-            # entries behind the rays' termination, which no kernel reads.  `traffic`: HBM bytes from rocprofv3 PMC (2 x FETCH_SIZE +
-            # WRITE_SIZE, profiles/pmc_traffic.json), `frac_traffic` = traffic / duration / peak.
-            "roofline": {"bound": "hbm", "kernel": f"gut_{dom}",
-                         "achieved": (touched if touched else model[dom]) / (stages[dom] * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": (touched if touched else model[dom]) / (stages[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "touched_bytes": touched, "traffic": traffic,
-                         "frac_traffic": (traffic / (stages[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
-                         "model_bytes": model[dom], "model_frac": achieved / HBM_PEAK_GBS, "kernel_ms": stages[dom],
-                         "entries": {"I": int(st.num_intersections), "fwd_evaluated": int(work.fwd_entries_evaluated),
-                                     "fwd_accepted": int(work.fwd_entries_accepted), "bwd_evaluated": int(work.bwd_entries_evaluated),
-                                     "bwd_accepted": int(work.bwd_entries_accepted)}},
-            # the compositing sweeps are bound by fp32 VALU issue, not by HBM: see valu_fraction()
-            "valu": valu_fraction(dom, stages[dom]),
-            "stages_ms": stages,
-            "stages_note": f"{abi.GUT_STAGES[dom_index]}: HIP events inside the timed region; the other stages: an all-stage pass of "
-                           f"{min(args.steps, 20)} steps before it (event pairs around every stage cost ~80 us of stream idle per step)",
-            "stage_bytes": model,
-            "frame_algorithmic_gb": total_bytes / 1e9,
-            "frame_hbm_frac": (total_bytes / (dt / args.steps)) / 1e9 / HBM_PEAK_GBS,
-            "work": {"N": int(st.num_particles), "Nv": int(st.num_visible), "I": int(st.num_intersections), "P": P,
-                     "tiles": int(st.num_tiles), "tile_key_bits": int(st.key_bits)},
         }
+        if args.full:
+            # every stage from the all-stage pass; the dominant kernel from the timed region itself
+            stages = {k: float(stage_all[i]) for i, k in enumerate(abi.GUT_STAGES)}
+            stages[abi.GUT_STAGES[dom_index]] = float(stage_ms[dom_index])
+            model = byte_model(int(st.num_particles), int(st.num_visible), int(st.num_intersections), P, int(st.key_bits))
+            dom = max(stages, key=lambda k: stages[k])
+            achieved = model[dom] / (stages[dom] * 1e-3) / 1e9
+            traffic = None
+            pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(pmc):
+                try:
+                    traffic = json.load(open(pmc)).get(args.workload, {}).get(dom)
+                except Exception:
+                    traffic = None
+            touched = touched_bytes(dom, work, P, int(st.num_intersections))
+            total_bytes = sum(model.values())
+            result.update({
+                # `achieved` / `frac`: bytes the kernel can actually touch (evaluated entries, counted on the device) / its duration.
+                # `model_*`: SURVEY §8d's per-entry byte model applied to ALL I tile entries — an upper bound that charges the 88 % of the
+                # entries behind the rays' termination, which no kernel reads.  `traffic`: HBM bytes from rocprofv3 PMC (2 x FETCH_SIZE +
+                # WRITE_SIZE, profiles/pmc_traffic.json), `frac_traffic` = traffic / duration / peak.
+                "roofline": {"bound": "hbm", "kernel": f"gut_{dom}",
+                             "achieved": (touched if touched else model[dom]) / (stages[dom] * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": (touched if touched else model[dom]) / (stages[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             "touched_bytes": touched, "traffic": traffic,
+                             "frac_traffic": (traffic / (stages[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
+                             "model_bytes": model[dom], "model_frac": achieved / HBM_PEAK_GBS, "kernel_ms": stages[dom],
+                             "entries": {"I": int(st.num_intersections), "fwd_evaluated": int(work.fwd_entries_evaluated),
+                                         "fwd_accepted": int(work.fwd_entries_accepted), "bwd_evaluated": int(work.bwd_entries_evaluated),
+                                         "bwd_accepted": int(work.bwd_entries_accepted)}},
+                # the compositing sweeps are bound by fp32 VALU issue, not by HBM: see valu_fraction()
+                "valu": valu_fraction(dom, stages[dom]),
+                "stages_ms": stages,
+                "stages_note": f"{abi.GUT_STAGES[dom_index]}: HIP events inside the timed region; the other stages: an all-stage pass of "
+                               f"{min(args.steps, 20)} steps before it (event pairs around every stage cost ~80 us of stream idle per step)",
+                "stage_bytes": model,
+                "frame_algorithmic_gb": total_bytes / 1e9,
+                "frame_hbm_frac": (total_bytes / (dt / args.steps)) / 1e9 / HBM_PEAK_GBS,
+            })
+        result["work"] = {"N": int(st.num_particles), "Nv": int(st.num_visible), "I": int(st.num_intersections), "P": P,
+                          "tiles": int(st.num_tiles), "tile_key_bits": int(st.key_bits)}
         if exchange is not None:
             result["exchange"] = exchange
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline()
-        if world == 1 and not args.no_secondary and args.workload == "c4_1m_1080p":
+        if args.full and world == 1 and not args.no_secondary and args.workload == "c4_1m_1080p":
             # the metric's second half.  NeRF-Synthetic Lego is not available offline: a synthetic teacher at BASELINE config 1's scale
             # (100 k Gaussians, 8 views at 400x400) is trained back from a perturbed copy for 500 SelectiveAdam steps through each
             # plugin, the way trainer.py drives it (3dgrut_amd/surrogate.py).  PSNR here is HIP-rendered on both sides;
@@ -697,7 +768,7 @@ def main():
                                                     "wall_s": time.time() - t0}
             # BASELINE config 3 in the same line (the driver runs the default command only): 3DGRT software-BVH primary rays,
             # BVH rebuilt + forward + backward per step, 1 M Gaussians at 800x800 — few steps, ~1 s
-            sec = argparse.Namespace(steps=5, warmup=2, workload="c3_grt_1m_800")
+            sec = argparse.Namespace(steps=5, warmup=2, workload="c3_grt_1m_800", full=True, dump_outputs=None)
             gn, gw, gh, gms = WORKLOADS["c3_grt_1m_800"]
             r = bench_grt(sec, 1, 0, dev, None, gn, gw, gh, gms, name="c3_grt_1m_800", emit=False)
             result["secondary"] = {"c3_grt_1m_800": {k: r[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "config", "stages_ms",
@@ -708,7 +779,7 @@ def main():
             import subprocess
             for small in ("c2_1m_800", "c1_100k_400"):
                 try:
-                    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", small, "--no-cpu-baseline", "--no-secondary",
+                    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", small, "--full", "--no-cpu-baseline", "--no-secondary",
                                           "--steps", str(args.steps), "--warmup", str(args.warmup)], capture_output=True, text=True, timeout=300).stdout
                     c2 = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
                     result["secondary"][small] = {k: c2[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "config", "stages_ms", "work")}

@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/${TAG}_variants.txt
 : > $OUT
 for v in "$@"; do
   if [ "$v" = "base" ]; then unset GRUT_AMD_LIB; else export GRUT_AMD_LIB=$R/variants/libgrut_amd_$v.so; fi
-  line=$(python $R/bench.py --no-cpu-baseline ${BENCH_ARGS} 2>/dev/null | tail -1)
+  line=$(python $R/bench.py --full --no-cpu-baseline ${BENCH_ARGS} 2>/dev/null | tail -1)
   echo "$v $line" | python -c "
 import sys, json
 name, rest = sys.stdin.read().split(' ', 1)

@@ -11,10 +11,10 @@ cd /tmp && export TMPDIR=/tmp
 O=/tmp/prof_$TAG          # raw rocprofv3 databases stay on the box (gpurun_out/ is capped at 64 MiB)
 S=$R/gpurun_out/summ_$TAG  # text summaries travel back
 mkdir -p $O $S
-GUT="python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-secondary"   # (--no-secondary: no 3DGRT / training-surrogate kernels in the averages)
-GRT="python $R/bench.py --workload c3_grt_1m_800 --steps 2 --warmup 1 --no-cpu-baseline"
+GUT="python $R/bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-secondary"   # (--no-secondary: no 3DGRT / training-surrogate kernels in the averages)
+GRT="python $R/bench.py --workload c3_grt_1m_800 --steps 2 --warmup 1 --full --no-cpu-baseline"
 # the timing pass runs bench.py's default step counts (clocks settle over the first steps; 4 steps read ~6 % slow)
-rocprofv3 --kernel-trace --stats -d $O/prof_${TAG}_stats -o st -- python $R/bench.py --no-cpu-baseline --no-secondary > $O/prof_${TAG}_stats.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/prof_${TAG}_stats -o st -- python $R/bench.py --full --no-cpu-baseline --no-secondary > $O/prof_${TAG}_stats.log 2>&1
 [ "$ONLY" = "stats" ] && { python $R/scripts/rocprof_summary.py stats $O/prof_${TAG}_stats/st_results.db > $S/kernel_stats.txt; python $R/bench.py > $S/bench.json 2> $S/bench.err; tail -c 300 $S/bench.json; exit 0; }
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/prof_${TAG}_fetch -o f -- $GUT > $O/prof_${TAG}_fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/prof_${TAG}_write -o w -- $GUT > $O/prof_${TAG}_write.log 2>&1

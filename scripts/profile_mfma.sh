@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd /tmp && export TMPDIR=/tmp
 O=/tmp/prof_mfma; S=$R/gpurun_out/summ_r05_mfma
 mkdir -p $O $S
-B="python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-secondary"
+B="python $R/bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-secondary"
 PMC="SQ_INSTS_VALU SQ_INSTS_VALU_MFMA_F32 SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES"
 rocprofv3 --kernel-trace --pmc $PMC -d $O/base -o b -- $B > $O/base.log 2>&1
 GRUT_AMD_LIB=$R/variants/libgrut_amd_mfma2_w6.so rocprofv3 --kernel-trace --pmc $PMC -d $O/mfma -o m -- $B > $O/mfma.log 2>&1

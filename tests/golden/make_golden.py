@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Generates tests/golden/per_hit_deg{2,4}.npz, adam.npz, camera.npz, projector.npz, grt_proxies.npz, grt_trace.npz and
+"""Generates tests/golden/per_hit_deg{2,4}.npz, gut_hit_seed77.npz, adam.npz, camera.npz, projector.npz, grt_proxies.npz, grt_trace.npz and
 gut_render.npz from the REFERENCE's own per-hit math, optimizer kernel, camera projection code, projection stage, 3DGRT
 proxy kernels and OptiX programs, and 3DGUT projection / render / renderBackward kernels.
 
@@ -129,6 +129,31 @@ def run(degree, n=512, seed=1234):
     print(path, f"accepted gut {gut_fwd_acc.mean():.2f} grt {grt_acc.mean():.2f} custom {custom_ok.mean():.2f} instance {inst_ok.mean():.2f}")
 
 
+
+
+def make_gut_hit_seed77(n=200):
+    """gut_hit_seed77.npz: the 3DGUT per-hit forward of libref_gut_hit_deg2.so on n random cases (seed 77), one particle and one ray
+    aimed near it per case (tests/test_oracle_cpu.py::test_gut_per_hit_live_against_reference_library)."""
+    lib = C.CDLL(os.path.join(REF, "libref_gut_hit_deg2.so"))
+    r = np.random.default_rng(77)
+    out = {k: [] for k in ("density12", "ray_o", "ray_d", "feat3", "state5", "ref_accept", "ref_state5")}
+    for _ in range(n):
+        pos = r.uniform(-1, 1, 3)
+        scl = np.exp(r.normal(np.log(0.1), 0.6, 3))
+        q = r.normal(size=4)
+        q /= np.linalg.norm(q)
+        d12 = np.concatenate([pos, [r.uniform(0.02, 1)], q, scl, [0]]).astype(F)
+        ro = r.uniform(-4, 4, 3).astype(F)
+        rd = pos + r.normal(size=3) * scl.mean() - ro
+        rd = (rd / np.linalg.norm(rd)).astype(F)
+        feat = r.uniform(0, 1, 3).astype(F)
+        st0 = np.array([r.uniform(0.1, 1), 0.1, 0.2, 0.3, 0.5], F)
+        st = st0.copy()
+        acc = lib.ref_gut_process_hit_fwd(_p(ro), _p(rd), _p(d12), _p(feat), C.c_float(MIN_RESPONSE), C.c_float(MIN_ALPHA), _p(st))
+        for k, v in zip(out, (d12, ro, rd, feat, st0, acc, st)):
+            out[k].append(v)
+    np.savez_compressed(os.path.join(HERE, "gut_hit_seed77.npz"), **{k: np.asarray(v) for k, v in out.items()})
+    print("wrote gut_hit_seed77.npz", n, "cases,", int(np.sum(out["ref_accept"])), "accepted")
 
 
 def make_adam():
@@ -918,12 +943,14 @@ def make_playground():
 if __name__ == "__main__":
     import sys
     only = [a for a in sys.argv[1:] if a.startswith("--only=")]
-    which = only[0][len("--only="):].split(",") if only else ["per_hit", "adam", "camera", "projector", "grt_proxies", "grt_trace", "grt_trace_mesh", "gut_render", "playground", "gut_nht", "grt_trace_nht", "grt_trace_nht_mesh", "grt_trace_slang_sh", "grt_trace_sphere", "grt_trace_bary"]
+    which = only[0][len("--only="):].split(",") if only else ["per_hit", "adam", "camera", "projector", "grt_proxies", "grt_trace", "grt_trace_mesh", "gut_render", "playground", "gut_nht", "grt_trace_nht", "grt_trace_nht_mesh", "grt_trace_slang_sh", "grt_trace_sphere", "grt_trace_bary", "gut_hit_seed77"]
     if "--adam-only" in sys.argv:
         which = ["adam"]
     if "per_hit" in which:
         for d in (2, 4):
             run(d)
+    if "gut_hit_seed77" in which:
+        make_gut_hit_seed77()
     if "adam" in which:
         make_adam()
     if "camera" in which:

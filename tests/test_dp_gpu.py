@@ -80,7 +80,7 @@ def test_bench_multi_rank_line_over_gloo_on_one_gpu(exchange):
     if "chunks" in exchange:
         env["GRUT_BENCH_EXCHANGE_CHUNKS"] = "4"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "c1_100k_400",
-                        "--no-cpu-baseline", "--no-secondary"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--no-secondary"], env=env, capture_output=True, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
     line = json.loads(lines[0])

@@ -1,8 +1,8 @@
 """CPU: pins the oracle (oracle/*.c, the CPU restatement used as checker) to the REFERENCE's own per-hit math.
 
 tests/golden/per_hit_deg{2,4}.npz were produced by the reference's source headers compiled on the host
-(tests/golden/make_golden.py, oracle/ref/).  Where oracle/_ref/ is present (build container), the same comparison is
-repeated live on fresh seeds.  Further CPU checks: analytic backward of the oracle against central finite differences
+(tests/golden/make_golden.py, oracle/ref/), and so was tests/golden/gut_hit_seed77.npz; where oracle/_ref/ is built, that
+library is also called live on the same cases.  Further CPU checks: analytic backward of the oracle against central finite differences
 of its own forward in float64, and basic invariants of the binning restatement.
 """
 import ctypes as C
@@ -67,28 +67,24 @@ def test_sh_radiance_matches_reference_vectors():
             assert _close(got, g["sh_radiance"][deg, i], rtol=1e-5, atol=1e-6), (i, deg)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(HERE), "oracle", "_ref", "libref_gut_hit_deg2.so")),
-                    reason="oracle/_ref is built only where /root/reference is mounted")
 def test_gut_per_hit_live_against_reference_library():
-    ref = C.CDLL(os.path.join(os.path.dirname(HERE), "oracle", "_ref", "libref_gut_hit_deg2.so"))
-    r = np.random.default_rng(77)
+    """200 random cases (seed 77) against the reference library's answers stored in tests/golden/gut_hit_seed77.npz
+    (make_golden.py --only=gut_hit_seed77); where oracle/_ref/ is built, the library is also called live on the same cases."""
+    g = np.load(os.path.join(HERE, "golden", "gut_hit_seed77.npz"))
+    lib = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "libref_gut_hit_deg2.so")
+    ref = C.CDLL(lib) if os.path.exists(lib) else None
     p = lambda a: a.ctypes.data_as(C.c_void_p)
     fl = C.c_float
-    for _ in range(200):
-        pos = r.uniform(-1, 1, 3)
-        scl = np.exp(r.normal(np.log(0.1), 0.6, 3))
-        q = r.normal(size=4)
-        q /= np.linalg.norm(q)
-        d12 = np.concatenate([pos, [r.uniform(0.02, 1)], q, scl, [0]]).astype(np.float32)
-        ro = r.uniform(-4, 4, 3).astype(np.float32)
-        rd = pos + r.normal(size=3) * scl.mean() - ro
-        rd = (rd / np.linalg.norm(rd)).astype(np.float32)
-        feat = r.uniform(0, 1, 3).astype(np.float32)
-        st0 = np.array([r.uniform(0.1, 1), 0.1, 0.2, 0.3, 0.5], np.float32)
-        st_ref = st0.copy()
-        acc_ref = ref.ref_gut_process_hit_fwd(p(ro), p(rd), p(d12), p(feat), fl(0.0113), fl(1 / 255), p(st_ref))
+    assert g["ray_o"].shape[0] == 200
+    for i in range(g["ray_o"].shape[0]):
+        ro, rd, d12, feat, st0 = (np.ascontiguousarray(g[k][i]) for k in ("ray_o", "ray_d", "density12", "feat3", "state5"))
+        acc_ref, st_ref = int(g["ref_accept"][i]), g["ref_state5"][i]
+        if ref is not None:
+            st_live = st0.copy()
+            assert ref.ref_gut_process_hit_fwd(p(ro), p(rd), p(d12), p(feat), fl(0.0113), fl(1 / 255), p(st_live)) == acc_ref
+            assert np.array_equal(st_live, st_ref), i
         acc, st = oracle.gut_process_hit_fwd(2, 0.0113, 1 / 255, 0.99, ro, rd, d12, feat, st0)
-        assert acc == acc_ref and _close(st, st_ref)
+        assert acc == acc_ref and _close(st, st_ref), i
 
 
 def _fd_check(scene, n_probe=12, eps=1e-6, **cfg_kw):
