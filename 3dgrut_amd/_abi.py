@@ -153,6 +153,7 @@ EXPORTED_SYMBOLS = [
     "grt_create", "grt_destroy", "grt_build_bvh", "grt_forward", "grt_backward", "grt_timings", "grt_stats", "grt_debug_fetch_work",
     "grt_debug_forward_hits", "grt_debug_fetch_instances", "grt_debug_fetch_custom_boxes", "grt_debug_fetch_lists", "grt_debug_backward_signature", "grt_build_mesh_bvh", "grt_trace_hybrid",
     "grut_selective_adam_update", "grut_pack_particles", "grut_unpack_particle_grads", "grut_activate_pack", "grut_activate_pack_backward",
+    "grut_mcmc_relocation", "grut_mcmc_perturb",
     "grut_last_error", "grut_abi_version", "grut_set_allocator", "gut_trim", "grt_trim",
 ]
 
@@ -253,6 +254,10 @@ def _declare(lib):
     lib.grut_activate_pack.restype = C.c_int
     lib.grut_activate_pack_backward.argtypes = [vp, C.c_uint32] + [fp] * 8
     lib.grut_activate_pack_backward.restype = C.c_int
+    lib.grut_mcmc_relocation.argtypes = [vp, C.c_uint32, fp, fp, ip, fp, C.c_int, fp, fp]
+    lib.grut_mcmc_relocation.restype = C.c_int
+    lib.grut_mcmc_perturb.argtypes = [vp, C.c_uint32, fp, fp, fp, fp, fp, C.c_float, C.c_float, C.c_int]
+    lib.grut_mcmc_perturb.restype = C.c_int
     lib.grut_last_error.argtypes = []
     lib.grut_last_error.restype = C.c_char_p
     lib.grut_abi_version.argtypes = []

@@ -526,6 +526,23 @@ int grut_activate_pack_backward(void* stream, uint32_t num_particles, const floa
                                 const float* raw_scale, const float* grad_particle_density, float* grad_positions,
                                 float* grad_raw_density, float* grad_raw_rotation, float* grad_raw_scale);
 
+/* ---- MCMC densification strategy (threedgrut/strategy/mcmc.py) ---------------------------------------------- */
+/* Replaces compute_relocation_kernel (threedgrut/strategy/src/gaussian_mcmc.cu:36-66, host side :70-92), one lane per sampled
+ * Gaussian: new_opacities[i] = 1 - (1 - opacities[i])^(1/n), new_scales[i] = opacities[i] / D * scales[i] with
+ * D = sum_{a=1..n} sum_{k=0..a-1} binoms[(a-1) n_max + k] (-1)^k / sqrt(k+1) new_opacities[i]^(k+1), summed in that order in fp32.
+ * n = ratios[i] clamped to [1, n_max] (the reference's caller clamps, mcmc.py:203-205; the clamp keeps every table read in bounds).
+ * Device tensors: opacities / new_opacities [n], scales / new_scales [n,3], ratios int32 [n], binoms [n_max, n_max]. */
+int grut_mcmc_relocation(void* stream, uint32_t n, const float* opacities, const float* scales, const int32_t* ratios,
+                         const float* binoms, int n_max, float* new_opacities, float* new_scales);
+/* Replaces MCMCStrategy.perturb_gaussians after its noise draw (threedgrut/strategy/mcmc.py:169-187, with get_covariance of
+ * model.py:120-130 and quaternion_to_so3 of utils/misc.py:67-88) in one pass:
+ * positions += R S S^T R^T (noise * sigmoid(-100 ((1 - density) - 0.995)) * noise_lr * lr), IN PLACE.
+ * activated = 0: rotation [n,4] / scale [n,3] / density [n,1] are the model's RAW parameters and normalize / exp / sigmoid are
+ * applied here (the defaults of configs/base_gs.yaml); activated = 1: they are already activated.  noise [n,3] is the caller's
+ * torch.randn_like(positions) (the random generator stays the caller's).  rotation 16-byte aligned; nothing is allocated. */
+int grut_mcmc_perturb(void* stream, uint32_t n, float* positions, const float* rotation, const float* scale, const float* density,
+                      const float* noise, float noise_lr, float lr, int activated);
+
 /* ---- optimizer step --------------------------------------- */
 /* One parameter group of SelectiveAdam (threedgrut/optimizers/__init__.py:85-124): contiguous fp32 [num_rows, row_width]
  * DEVICE tensors, 16-byte aligned. */

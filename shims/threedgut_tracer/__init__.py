@@ -8,5 +8,7 @@ _root = _os.path.dirname(_os.path.dirname(_os.path.dirname(_os.path.abspath(__fi
 if _root not in _sys.path:
     _sys.path.insert(0, _root)
 Tracer = _il.import_module("3dgrut_amd.gut_tracer").Tracer
+# the MCMC strategy's plugin (threedgrut/strategy/mcmc.py:41 `from . import lib_mcmc_cc`): registered before any strategy exists
+_il.import_module("3dgrut_amd.mcmc").install()
 
 __all__ = ["Tracer"]
