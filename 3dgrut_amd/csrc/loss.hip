@@ -1,0 +1,371 @@
+// loss.hip — fused, differentiable SSIM: the device side of the `fused_ssim` package the reference's loss imports
+// (threedgrut/model/losses.py:17, called at :31-33 with padding="valid"; trainer.py:715-720 evaluates it on every step).
+//
+//   map = ((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)),   mu = G*x, s1 = G*(xx) - mu1^2, s12 = G*(xy) - mu1 mu2
+//   G: separable 11-tap Gaussian (sigma 1.5), zero padding, per channel and per image of the batch.
+//
+//   * forward: one workgroup per 32x32 output tile.  Tile + 5-pixel halo of both images -> LDS (bounds-checked loads: no padded copy),
+//     horizontal pass of the five window sums (x, y, xx, yy, xy) -> LDS, vertical pass -> registers, then the map and, when training,
+//     the three partial-derivative planes dmap/dmu1 (with the dependence of s1 and s12 on mu1 folded in), dmap/ds1, dmap/ds12.  The tile's
+//     map is summed in a fixed order (lane-sequential, DPP wave sum, four waves in order) into ONE partial per workgroup; a second launch
+//     of one workgroup adds the partials in fp64 in a fixed order and writes the mean.  No floating-point atomics: bitwise reproducible.
+//   * backward: dL/dimg1 = G*(dL dm_dmu1) + 2 img1 G*(dL dm_ds1) + img2 G*(dL dm_ds12), dL = grad_out / count inside the counted region
+//     (the 5-pixel crop of "valid") and 0 outside; same tiling, three window sums instead of five.  grad_out is read from device memory.
+//
+// Layout.  Both kernels take element strides for (B, C, H, W).  NC channels are handled by one workgroup: NC = 1 for planar (NCHW)
+// memory, NC = C (2..4) for an NCHW view of channels-last memory (stride_c == 1, stride_w == C: what trainer.py:717-718 passes).  The
+// staging loop walks a tile row as (pixel, channel) pairs, which for channels-last memory is ONE contiguous run of 42 NC (forward) or
+// 32 NC (backward, and its gradient store) words, so consecutive lanes touch consecutive addresses in either layout; the channels are
+// de-interleaved on the way into LDS so that both passes read unit-stride rows.  Any other stride pattern runs with NC = 1: correct,
+// with strided loads.  The derivative planes are private: planar [B, C, H, W].
+//
+// Sizes.  Tile 32x32, 256 threads (4 waves).  A 32-wide tile makes a row of the horizontal result exactly one 32-lane LDS access group
+// (ds_read_b32 / ds_write_b32 are served in two 32-lane halves, bank = word mod 32: unit-stride rows never conflict, and the staged rows'
+// pitch of 42 words only matters across halves, which do not interact).  The halo costs (42/32)^2 = 1.72x loads, absorbed by L2; a 64x64
+// tile (1.34x) would need 2.4x the LDS.  LDS per workgroup, forward: 2 NC 42x42 staged + 5 x 42x32 horizontal sums = 40.0 KiB (NC = 1),
+// 67.6 KiB (NC = 3), 81.4 KiB (NC = 4); backward: 3 x 42x42 + 3 x 42x32 + 2 NC 32x32 = 44.4 KiB (NC = 1), 60.4 KiB (NC = 3).  Of the CU's
+// 160 KiB that is 3 / 2 / 1 resident workgroups forward and 3 / 2 backward; the horizontal sums are kept per channel (not 5 NC planes)
+// precisely so that RGB keeps two.  The vertical pass gives each lane a 4-row strip of one column (14 LDS reads per 4 outputs and sum);
+// the forward uses 84 (NC = 1) to 110 (NC = 4) VGPRs, under the 128 that 4 waves per SIMD would allow, and LDS caps residency at 3
+// workgroups = 3 waves per SIMD anyway, hence amdgpu_waves_per_eu(1, 4): no register squeeze for an occupancy LDS forbids.
+// Byte model (P = B C H W): forward training reads 8P and writes 12P, backward reads 20P and writes 4P, inference reads 8P.
+#include <algorithm>
+
+#include "common.hpp"
+
+namespace grut {
+
+constexpr int kSsimThreads = 256, kSsimTile = 32, kSsimHalo = 5, kSsimSpan = kSsimTile + 2 * kSsimHalo, kSsimTaps = 11, kSsimStrip = 4;
+static_assert(kSsimThreads == kSsimTile * (kSsimTile / kSsimStrip), "one lane per column and 4-row strip");
+// exp(-(i-5)^2 / (2 1.5^2)) normalised to sum 1 in double, rounded to fp32 (9 significant digits reproduce the fp32 value exactly)
+static __device__ const float kSsimTap[kSsimTaps] = {0.00102838012f, 0.00759875821f, 0.0360007733f, 0.109360687f, 0.213005543f, 0.266011715f,
+                                                      0.213005543f,   0.109360687f,   0.0360007733f, 0.00759875821f, 0.00102838012f};
+constexpr float kSsimC1 = 0.01f * 0.01f, kSsimC2 = 0.03f * 0.03f;
+
+struct SsimView {   // an NCHW view: element strides
+    const float* p;
+    long long sb, sc, sh, sw;
+    __device__ __forceinline__ float at(int b, int c, int y, int x) const { return p[b * sb + c * sc + y * sh + x * sw]; }
+};
+struct SsimShape {
+    int C, H, W, valid;
+};
+
+// the 4-row strip of column x: out[j] = sum_k tap[k] * rows[ys + j + k][x]
+template <typename Rows>
+__device__ __forceinline__ void ssim_vertical(const Rows& rows, int ys, int x, float (&out)[kSsimStrip]) {
+    float v[kSsimStrip + kSsimTaps - 1];
+#pragma unroll
+    for (int i = 0; i < kSsimStrip + kSsimTaps - 1; ++i) v[i] = rows[ys + i][x];
+#pragma unroll
+    for (int j = 0; j < kSsimStrip; ++j) {
+        float s = 0.0f;
+#pragma unroll
+        for (int k = 0; k < kSsimTaps; ++k) s = fmaf(kSsimTap[k], v[j + k], s);
+        out[j] = s;
+    }
+}
+
+// Staging loop: element i of TOTAL is produced by load(i) (global memory, N words) and consumed by store(i, words) (LDS).  Written as
+// "request kSsimBatch elements, then store them" because a plain load-store loop has ONE request per lane in flight: with at most 12
+// waves per CU that made both kernels wait on HBM latency ~21 times in a row per tile (forward 127 us at 1080p RGB, 1.0 TB/s by the
+// byte model, before).
+constexpr int kSsimBatch = 8;
+template <int N>
+struct SsimWords {
+    float v[N];
+};
+template <int TOTAL, int N, typename Load, typename Store>
+__device__ __forceinline__ void ssim_stage(int t, Load load, Store store) {
+    for (int base = t; base < TOTAL; base += kSsimBatch * kSsimThreads) {
+        SsimWords<N> w[kSsimBatch];
+#pragma unroll
+        for (int k = 0; k < kSsimBatch; ++k) {
+            const int i = base + k * kSsimThreads;
+            if (i < TOTAL) w[k] = load(i);
+        }
+#pragma unroll
+        for (int k = 0; k < kSsimBatch; ++k) {
+            const int i = base + k * kSsimThreads;
+            if (i < TOTAL) store(i, w[k]);
+        }
+    }
+}
+
+__device__ __forceinline__ bool ssim_counted(const SsimShape& s, int y, int x) {   // the pixels the mean runs over
+    const int m = s.valid ? kSsimHalo : 0;
+    return y >= m && y < s.H - m && x >= m && x < s.W - m;
+}
+
+template <int NC, bool TRAIN>
+__global__ __launch_bounds__(kSsimThreads) __attribute__((amdgpu_waves_per_eu(1, 4))) void ssim_forward_kernel(
+    SsimShape shp, SsimView img1, SsimView img2, float* __restrict__ partials, float* __restrict__ dm_dmu1, float* __restrict__ dm_ds1,
+    float* __restrict__ dm_ds12) {
+    __shared__ float s_raw[2][NC][kSsimSpan][kSsimSpan];
+    __shared__ float s_h[5][kSsimSpan][kSsimTile];
+    __shared__ float s_red[kSsimThreads / GRUT_WAVE];
+    const int t = threadIdx.x, H = shp.H, W = shp.W;
+    const int x0 = blockIdx.x * kSsimTile, y0 = blockIdx.y * kSsimTile;
+    const int groups = shp.C / NC, b = blockIdx.z / groups, c0 = (blockIdx.z % groups) * NC;
+
+    constexpr int kRun = kSsimSpan * NC;   // one staged row as (pixel, channel) pairs: contiguous in channels-last memory
+    ssim_stage<kSsimSpan * kRun, 2>(
+        t,
+        [&](int i) {
+            const int r = i / kRun, j = i - r * kRun, px = j / NC, ch = j - px * NC;
+            const int y = y0 - kSsimHalo + r, x = x0 - kSsimHalo + px;
+            const bool in = y >= 0 && y < H && x >= 0 && x < W;
+            return SsimWords<2>{{in ? img1.at(b, c0 + ch, y, x) : 0.0f, in ? img2.at(b, c0 + ch, y, x) : 0.0f}};
+        },
+        [&](int i, const SsimWords<2>& w) {
+            const int r = i / kRun, j = i - r * kRun, px = j / NC, ch = j - px * NC;
+            s_raw[0][ch][r][px] = w.v[0];
+            s_raw[1][ch][r][px] = w.v[1];
+        });
+
+    const int x = t & (kSsimTile - 1), ys = (t / kSsimTile) * kSsimStrip;
+    float acc = 0.0f;
+    for (int ch = 0; ch < NC; ++ch) {
+        __syncthreads();   // the staged tile is complete / the previous channel's vertical pass has read s_h
+        for (int i = t; i < kSsimSpan * kSsimTile; i += kSsimThreads) {
+            const int r = i / kSsimTile, c = i & (kSsimTile - 1);
+            float m1 = 0.0f, m2 = 0.0f, xx = 0.0f, yy = 0.0f, xy = 0.0f;
+#pragma unroll
+            for (int k = 0; k < kSsimTaps; ++k) {
+                const float p = s_raw[0][ch][r][c + k], q = s_raw[1][ch][r][c + k];
+                const float wp = kSsimTap[k] * p, wq = kSsimTap[k] * q;
+                m1 += wp;
+                m2 += wq;
+                xx = fmaf(wp, p, xx);
+                yy = fmaf(wq, q, yy);
+                xy = fmaf(wp, q, xy);
+            }
+            s_h[0][r][c] = m1;
+            s_h[1][r][c] = m2;
+            s_h[2][r][c] = xx;
+            s_h[3][r][c] = yy;
+            s_h[4][r][c] = xy;
+        }
+        __syncthreads();
+        float o[5][kSsimStrip];
+#pragma unroll
+        for (int q = 0; q < 5; ++q) ssim_vertical(s_h[q], ys, x, o[q]);
+#pragma unroll
+        for (int j = 0; j < kSsimStrip; ++j) {
+            const int gy = y0 + ys + j, gx = x0 + x;
+            if (gy >= H || gx >= W) continue;
+            const float mu1 = o[0][j], mu2 = o[1][j];
+            const float mu1s = mu1 * mu1, mu2s = mu2 * mu2, mu12 = mu1 * mu2;
+            const float s1 = o[2][j] - mu1s, s2 = o[3][j] - mu2s, s12 = o[4][j] - mu12;
+            const float a1 = 2.0f * mu12 + kSsimC1, a2 = 2.0f * s12 + kSsimC2;
+            const float b1 = mu1s + mu2s + kSsimC1, b2 = s1 + s2 + kSsimC2;
+            const float den = b1 * b2;
+            const float map = (a1 * a2) / den;
+            if (ssim_counted(shp, gy, gx)) acc += map;
+            if constexpr (TRAIN) {
+                // map as a function of (mu1, E[xx], E[xy]): dmap/dE[xx] = dmap/ds1, dmap/dE[xy] = dmap/ds12, and the total derivative in
+                // mu1 carries ds1/dmu1 = -2 mu1 and ds12/dmu1 = -mu2
+                const float d_s1 = -map / b2;
+                const float d_s12 = (2.0f * a1) / den;
+                const float d_mu1 = (2.0f * a2) / den * (mu2 - mu1 * (a1 / b1)) - 2.0f * mu1 * d_s1 - mu2 * d_s12;
+                const size_t at = (((size_t)b * shp.C + (c0 + ch)) * H + gy) * W + gx;
+                dm_dmu1[at] = d_mu1;
+                dm_ds1[at] = d_s1;
+                dm_ds12[at] = d_s12;
+            }
+        }
+    }
+    acc = wave_sum(acc);
+    if ((t & (GRUT_WAVE - 1)) == 0) s_red[t / GRUT_WAVE] = acc;
+    __syncthreads();
+    if (t == 0) {
+        float s = s_red[0];
+        for (int w = 1; w < kSsimThreads / GRUT_WAVE; ++w) s += s_red[w];
+        partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// one workgroup: lane t adds partials t, t + 256, ... in fp64, then a fixed tree over the 256 lanes
+__global__ __launch_bounds__(kSsimThreads) void ssim_mean_kernel(const float* __restrict__ partials, uint32_t n, double inv_count,
+                                                                 float* __restrict__ out_mean) {
+    __shared__ double s_sum[kSsimThreads];
+    double s = 0.0;
+    for (uint32_t i = threadIdx.x; i < n; i += kSsimThreads) s += (double)partials[i];
+    s_sum[threadIdx.x] = s;
+    __syncthreads();
+    for (int half = kSsimThreads / 2; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half) s_sum[threadIdx.x] += s_sum[threadIdx.x + half];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out_mean[0] = (float)(s_sum[0] * inv_count);
+}
+
+template <int NC>
+__global__ __launch_bounds__(kSsimThreads) __attribute__((amdgpu_waves_per_eu(1, 4))) void ssim_backward_kernel(
+    SsimShape shp, SsimView img1, SsimView img2, const float* __restrict__ grad_out, float inv_count, const float* __restrict__ dm_dmu1,
+    const float* __restrict__ dm_ds1, const float* __restrict__ dm_ds12, float* __restrict__ grad, long long gsb, long long gsc, long long gsh,
+    long long gsw) {
+    __shared__ float s_x[kSsimTile][kSsimTile * NC], s_y[kSsimTile][kSsimTile * NC];   // (pixel, channel) pairs, as in memory
+    __shared__ float s_p[3][kSsimSpan][kSsimSpan];
+    __shared__ float s_h[3][kSsimSpan][kSsimTile];
+    const int t = threadIdx.x, H = shp.H, W = shp.W;
+    const int x0 = blockIdx.x * kSsimTile, y0 = blockIdx.y * kSsimTile;
+    const int groups = shp.C / NC, b = blockIdx.z / groups, c0 = (blockIdx.z % groups) * NC;
+    const float scale = grad_out[0] * inv_count;
+
+    constexpr int kRun = kSsimTile * NC;
+    ssim_stage<kSsimTile * kRun, 2>(
+        t,
+        [&](int i) {
+            const int r = i / kRun, j = i - r * kRun, px = j / NC, ch = j - px * NC;
+            const int y = y0 + r, x = x0 + px;
+            const bool in = y < H && x < W;
+            return SsimWords<2>{{in ? img1.at(b, c0 + ch, y, x) : 0.0f, in ? img2.at(b, c0 + ch, y, x) : 0.0f}};
+        },
+        [&](int i, const SsimWords<2>& w) {
+            const int r = i / kRun, j = i - r * kRun;
+            s_x[r][j] = w.v[0];
+            s_y[r][j] = w.v[1];
+        });
+
+    const int x = t & (kSsimTile - 1), ys = (t / kSsimTile) * kSsimStrip;
+    for (int ch = 0; ch < NC; ++ch) {
+        __syncthreads();   // the previous channel's passes are done with s_p and s_h
+        const size_t plane = ((size_t)b * shp.C + (c0 + ch)) * H;
+        ssim_stage<kSsimSpan * kSsimSpan, 3>(
+            t,
+            [&](int i) {
+                const int r = i / kSsimSpan, px = i - r * kSsimSpan;
+                const int y = y0 - kSsimHalo + r, xg = x0 - kSsimHalo + px;
+                const bool in = y >= 0 && xg >= 0 && ssim_counted(shp, y, xg);   // dL/dmap is 0 outside the counted region
+                const size_t at = in ? (plane + y) * W + xg : 0;
+                return SsimWords<3>{{in ? dm_dmu1[at] : 0.0f, in ? dm_ds1[at] : 0.0f, in ? dm_ds12[at] : 0.0f}};
+            },
+            [&](int i, const SsimWords<3>& w) {
+                const int r = i / kSsimSpan, px = i - r * kSsimSpan;
+                s_p[0][r][px] = w.v[0];
+                s_p[1][r][px] = w.v[1];
+                s_p[2][r][px] = w.v[2];
+            });
+        __syncthreads();
+        for (int i = t; i < kSsimSpan * kSsimTile; i += kSsimThreads) {
+            const int r = i / kSsimTile, c = i & (kSsimTile - 1);
+            float h0 = 0.0f, h1 = 0.0f, h2 = 0.0f;
+#pragma unroll
+            for (int k = 0; k < kSsimTaps; ++k) {
+                h0 = fmaf(kSsimTap[k], s_p[0][r][c + k], h0);
+                h1 = fmaf(kSsimTap[k], s_p[1][r][c + k], h1);
+                h2 = fmaf(kSsimTap[k], s_p[2][r][c + k], h2);
+            }
+            s_h[0][r][c] = h0;
+            s_h[1][r][c] = h1;
+            s_h[2][r][c] = h2;
+        }
+        __syncthreads();
+        float o[3][kSsimStrip];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) ssim_vertical(s_h[q], ys, x, o[q]);
+#pragma unroll
+        for (int j = 0; j < kSsimStrip; ++j) {   // each (row, pixel, channel) slot of s_x is read and overwritten by this lane alone
+            const float xv = s_x[ys + j][x * NC + ch], yv = s_y[ys + j][x * NC + ch];
+            s_x[ys + j][x * NC + ch] = scale * (o[0][j] + 2.0f * xv * o[1][j] + yv * o[2][j]);
+        }
+    }
+    __syncthreads();
+    for (int i = t; i < kSsimTile * kRun; i += kSsimThreads) {
+        const int r = i / kRun, j = i - r * kRun, px = j / NC, ch = j - px * NC;
+        const int y = y0 + r, xg = x0 + px;
+        if (y < H && xg < W) grad[b * gsb + (c0 + ch) * gsc + y * gsh + xg * gsw] = s_x[r][j];
+    }
+}
+
+// NC > 1 only for an NCHW view of channels-last memory with 2..4 channels (see the head of the file)
+static int ssim_channels_per_group(int C, int W, const int64_t* s) {
+    return (C >= 2 && C <= 4 && s[1] == 1 && s[3] == C && s[2] >= (int64_t)W * C) ? C : 1;
+}
+static dim3 ssim_grid(int B, int C, int H, int W, int nc) {
+    return dim3(div_up((uint32_t)W, kSsimTile), div_up((uint32_t)H, kSsimTile), (uint32_t)(B * (C / nc)));
+}
+static int ssim_check_shape(const char* who, int B, int C, int H, int W, int valid) {
+    GRUT_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1, "%s: B, C, H, W must be >= 1 (got %d, %d, %d, %d)", who, B, C, H, W);
+    GRUT_REQUIRE(valid == 0 || valid == 1, "%s: valid must be 0 (\"same\") or 1 (got %d)", who, valid);
+    GRUT_REQUIRE(!valid || (H >= kSsimTaps && W >= kSsimTaps), "%s: \"valid\" needs H, W >= 11 (got %d x %d)", who, H, W);
+    GRUT_REQUIRE((int64_t)B * C <= 65535, "%s: B * C must be <= 65535 (got %lld)", who, (long long)B * C);
+    return GRUT_OK;
+}
+static double ssim_count(int B, int C, int H, int W, int valid) {
+    const int m = valid ? 2 * kSsimHalo : 0;
+    return (double)B * C * (double)(H - m) * (double)(W - m);
+}
+
+template <int NC>
+static void ssim_launch_forward(bool train, dim3 grid, hipStream_t s, SsimShape shp, SsimView v1, SsimView v2, float* partials, float* dm_dmu1,
+                                float* dm_ds1, float* dm_ds12) {
+    if (train)
+        hipLaunchKernelGGL((ssim_forward_kernel<NC, true>), grid, dim3(kSsimThreads), 0, s, shp, v1, v2, partials, dm_dmu1, dm_ds1, dm_ds12);
+    else
+        hipLaunchKernelGGL((ssim_forward_kernel<NC, false>), grid, dim3(kSsimThreads), 0, s, shp, v1, v2, partials, (float*)nullptr,
+                           (float*)nullptr, (float*)nullptr);
+}
+
+}  // namespace grut
+
+extern "C" uint32_t grut_ssim_partials(int B, int C, int H, int W) {
+    using namespace grut;
+    if (B < 1 || C < 1 || H < 1 || W < 1) return 0;
+    return (uint32_t)B * (uint32_t)C * div_up((uint32_t)W, kSsimTile) * div_up((uint32_t)H, kSsimTile);
+}
+
+extern "C" int grut_ssim_forward(void* stream, int B, int C, int H, int W, const float* img1, const int64_t* stride1, const float* img2,
+                                 const int64_t* stride2, int valid, float* out_mean, float* partials, float* dm_dmu1, float* dm_ds1,
+                                 float* dm_ds12) {
+    using namespace grut;
+    GRUT_CHECK(ssim_check_shape("grut_ssim_forward", B, C, H, W, valid));
+    GRUT_REQUIRE(img1 && img2 && stride1 && stride2 && out_mean && partials, "grut_ssim_forward: null tensor");
+    const bool train = dm_dmu1 || dm_ds1 || dm_ds12;
+    GRUT_REQUIRE(!train || (dm_dmu1 && dm_ds1 && dm_ds12), "grut_ssim_forward: the three derivative planes are given together or not at all");
+    const int nc = std::min(ssim_channels_per_group(C, W, stride1), ssim_channels_per_group(C, W, stride2));
+    const dim3 grid = ssim_grid(B, C, H, W, nc);
+    const SsimShape shp{C, H, W, valid};
+    const SsimView v1{img1, stride1[0], stride1[1], stride1[2], stride1[3]}, v2{img2, stride2[0], stride2[1], stride2[2], stride2[3]};
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    switch (nc) {
+        case 2: ssim_launch_forward<2>(train, grid, s, shp, v1, v2, partials, dm_dmu1, dm_ds1, dm_ds12); break;
+        case 3: ssim_launch_forward<3>(train, grid, s, shp, v1, v2, partials, dm_dmu1, dm_ds1, dm_ds12); break;
+        case 4: ssim_launch_forward<4>(train, grid, s, shp, v1, v2, partials, dm_dmu1, dm_ds1, dm_ds12); break;
+        default: ssim_launch_forward<1>(train, grid, s, shp, v1, v2, partials, dm_dmu1, dm_ds1, dm_ds12); break;
+    }
+    GRUT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ssim_mean_kernel, dim3(1), dim3(kSsimThreads), 0, s, partials, grid.x * grid.y * grid.z,
+                       1.0 / ssim_count(B, C, H, W, valid), out_mean);
+    GRUT_HIP(hipGetLastError());
+    return GRUT_OK;
+}
+
+extern "C" int grut_ssim_backward(void* stream, int B, int C, int H, int W, const float* img1, const int64_t* stride1, const float* img2,
+                                  const int64_t* stride2, int valid, const float* grad_out, const float* dm_dmu1, const float* dm_ds1,
+                                  const float* dm_ds12, float* grad_img1, const int64_t* grad_stride) {
+    using namespace grut;
+    GRUT_CHECK(ssim_check_shape("grut_ssim_backward", B, C, H, W, valid));
+    GRUT_REQUIRE(img1 && img2 && stride1 && stride2 && grad_out && dm_dmu1 && dm_ds1 && dm_ds12 && grad_img1 && grad_stride,
+                 "grut_ssim_backward: null tensor");
+    const int nc = std::min(std::min(ssim_channels_per_group(C, W, stride1), ssim_channels_per_group(C, W, stride2)),
+                            ssim_channels_per_group(C, W, grad_stride));
+    const dim3 grid = ssim_grid(B, C, H, W, nc);
+    const SsimShape shp{C, H, W, valid};
+    const SsimView v1{img1, stride1[0], stride1[1], stride1[2], stride1[3]}, v2{img2, stride2[0], stride2[1], stride2[2], stride2[3]};
+    const float inv_count = (float)(1.0 / ssim_count(B, C, H, W, valid));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+#define GRUT_SSIM_BWD(NC)                                                                                                                \
+    hipLaunchKernelGGL((ssim_backward_kernel<NC>), grid, dim3(kSsimThreads), 0, s, shp, v1, v2, grad_out, inv_count, dm_dmu1, dm_ds1, dm_ds12, \
+                       grad_img1, (long long)grad_stride[0], (long long)grad_stride[1], (long long)grad_stride[2], (long long)grad_stride[3])
+    switch (nc) {
+        case 2: GRUT_SSIM_BWD(2); break;
+        case 3: GRUT_SSIM_BWD(3); break;
+        case 4: GRUT_SSIM_BWD(4); break;
+        default: GRUT_SSIM_BWD(1); break;
+    }
+#undef GRUT_SSIM_BWD
+    GRUT_HIP(hipGetLastError());
+    return GRUT_OK;
+}

@@ -543,6 +543,28 @@ int grut_mcmc_relocation(void* stream, uint32_t n, const float* opacities, const
 int grut_mcmc_perturb(void* stream, uint32_t n, float* positions, const float* rotation, const float* scale, const float* density,
                       const float* noise, float noise_lr, float lr, int activated);
 
+/* ---- fused SSIM loss (the `fused_ssim` package as called by threedgrut/model/losses.py:31-33) ------------------- */
+/* Both entry points replace fused_ssim(img1, img2, padding) of the CUDA-only third-party extension the reference's loss imports
+ * (threedgrut/model/losses.py:17; trainer.py:715-720 evaluates 1 - ssim on every step).  Window: separable 11-tap Gaussian, sigma 1.5,
+ * zero padding per channel and image; C1 = 0.01^2, C2 = 0.03^2; valid = 0: mean of the map over all B C H W pixels ("same"), valid = 1:
+ * over map[:, :, 5:-5, 5:-5] ("valid", needs H, W >= 11).
+ * Strides contract: img1 / img2 / grad_img1 are [B, C, H, W] fp32 DEVICE tensors addressed through ELEMENT strides for (B, C, H, W), so a
+ * contiguous NCHW tensor and an NCHW view of channels-last memory (stride_c = 1, stride_w = C, C <= 4: read as contiguous runs) are both
+ * read in place; any other non-negative strides are accepted and read element-wise.  Outputs and scratch belong to the caller:
+ * out_mean [1], partials [the companion below] and, when training, three planes of B C H W floats each (all three NULL: inference, no
+ * plane is written).  Nothing needs to be zeroed; every element of every buffer is written before it is read.  The result is bitwise
+ * reproducible (fixed-order reduction, no atomics); nothing synchronises with the host. */
+int grut_ssim_forward(void* stream, int B, int C, int H, int W, const float* img1, const int64_t* stride1, const float* img2,
+                      const int64_t* stride2, int valid, float* out_mean, float* partials, float* dm_dmu1, float* dm_ds1, float* dm_ds12);
+/* dL/dimg1 = G*(dL dm_dmu1) + 2 img1 G*(dL dm_ds1) + img2 G*(dL dm_ds12) with dL = grad_out[0] / count inside the counted region and 0
+ * outside (img2 is a constant: no gradient, as upstream).  grad_out [1] is read from DEVICE memory; grad_img1 is fully written through
+ * grad_stride (pass img1's strides and autograd has nothing to re-lay out). */
+int grut_ssim_backward(void* stream, int B, int C, int H, int W, const float* img1, const int64_t* stride1, const float* img2,
+                       const int64_t* stride2, int valid, const float* grad_out, const float* dm_dmu1, const float* dm_ds1,
+                       const float* dm_ds12, float* grad_img1, const int64_t* grad_stride);
+/* How many floats of `partials` the forward call may write for this shape (one per workgroup; 0 for a bad shape). */
+uint32_t grut_ssim_partials(int B, int C, int H, int W);
+
 /* ---- optimizer step --------------------------------------- */
 /* One parameter group of SelectiveAdam (threedgrut/optimizers/__init__.py:85-124): contiguous fp32 [num_rows, row_width]
  * DEVICE tensors, 16-byte aligned. */

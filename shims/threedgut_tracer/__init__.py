@@ -10,5 +10,7 @@ if _root not in _sys.path:
 Tracer = _il.import_module("3dgrut_amd.gut_tracer").Tracer
 # the MCMC strategy's plugin (threedgrut/strategy/mcmc.py:41 `from . import lib_mcmc_cc`): registered before any strategy exists
 _il.import_module("3dgrut_amd.mcmc").install()
+# the loss's extension (threedgrut/model/losses.py:17 `from fused_ssim import fused_ssim`): the HIP fused SSIM unless one is installed
+_il.import_module("3dgrut_amd.losses").install()
 
 __all__ = ["Tracer"]
