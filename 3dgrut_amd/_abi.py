@@ -154,6 +154,7 @@ EXPORTED_SYMBOLS = [
     "grt_debug_forward_hits", "grt_debug_fetch_instances", "grt_debug_fetch_custom_boxes", "grt_debug_fetch_lists", "grt_debug_backward_signature", "grt_build_mesh_bvh", "grt_trace_hybrid",
     "grut_selective_adam_update", "grut_pack_particles", "grut_unpack_particle_grads", "grut_activate_pack", "grut_activate_pack_backward",
     "grut_mcmc_relocation", "grut_mcmc_perturb",
+    "grut_densify_accumulate", "grut_relayout_scan", "grut_relayout_scratch_bytes", "grut_relayout_rows", "grut_split_tail",
     "grut_ssim_forward", "grut_ssim_backward", "grut_ssim_partials",
     "grut_last_error", "grut_abi_version", "grut_set_allocator", "gut_trim", "grt_trim",
 ]
@@ -259,6 +260,16 @@ def _declare(lib):
     lib.grut_mcmc_relocation.restype = C.c_int
     lib.grut_mcmc_perturb.argtypes = [vp, C.c_uint32, fp, fp, fp, fp, fp, C.c_float, C.c_float, C.c_int]
     lib.grut_mcmc_perturb.restype = C.c_int
+    lib.grut_densify_accumulate.argtypes = [vp, C.c_uint32, fp, fp, fp, C.c_int64, fp, ip]
+    lib.grut_densify_accumulate.restype = C.c_int
+    lib.grut_relayout_scan.argtypes = [vp, C.c_uint32, up, up, up, up, up, vp, C.c_uint64]
+    lib.grut_relayout_scan.restype = C.c_int
+    lib.grut_relayout_scratch_bytes.argtypes = [C.c_uint32]
+    lib.grut_relayout_scratch_bytes.restype = C.c_uint64
+    lib.grut_relayout_rows.argtypes = [vp, C.c_uint32, C.c_uint32, vp, up, up, up, up, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, vp]
+    lib.grut_relayout_rows.restype = C.c_int
+    lib.grut_split_tail.argtypes = [vp, C.c_uint32, fp, fp, fp, fp, C.c_uint32]
+    lib.grut_split_tail.restype = C.c_int
     strides = C.POINTER(C.c_int64)   # int64_t[4]: element strides of (B, C, H, W)
     lib.grut_ssim_forward.argtypes = [vp] + [C.c_int] * 4 + [fp, strides, fp, strides, C.c_int, fp, fp, fp, fp, fp]
     lib.grut_ssim_forward.restype = C.c_int

@@ -543,6 +543,39 @@ int grut_mcmc_relocation(void* stream, uint32_t n, const float* opacities, const
 int grut_mcmc_perturb(void* stream, uint32_t n, float* positions, const float* rotation, const float* scale, const float* density,
                       const float* noise, float noise_lr, float lr, int activated);
 
+/* ---- default densification strategy (threedgrut/strategy/gs.py) ------------------------------------------------ */
+/* None of these allocates or synchronises; every tensor is a contiguous DEVICE tensor of the caller. */
+/* Replaces GSStrategy.update_gradient_buffer (gs.py:131-139) in one pass: for every row with a non-zero (or NaN) component of
+ * positions_grad [n,3]: accum[i] += || positions_grad[i] * ||positions[i] - c||_2 ||_2 / 2 and denom[i] += 1 (accum fp32 [n], denom
+ * int32 [n]); all other rows of both buffers are left untouched.  c is read from DEVICE memory at sensor_position[0],
+ * [sensor_stride], [2 sensor_stride] (element stride: the caller's T_to_world[0, :3, 3] view has stride 4 and is read in place). */
+int grut_densify_accumulate(void* stream, uint32_t n, const float* positions_grad, const float* positions,
+                            const float* sensor_position, int64_t sensor_stride, float* accum, int32_t* denom);
+enum { GRUT_APPEND_COPY = 0,   /* the appended block holds copies of the selected rows */
+       GRUT_APPEND_ZERO = 1    /* the appended block is zeros (the optimizer's moments of new Gaussians) */ };
+/* The destinations of the boolean indexing in clone_gaussians / split_gaussians / prune_* (gs.py:154-283): keep / append are byte
+ * masks [n] (torch bool storage); keep = NULL means every row, append = NULL none.  Writes the exclusive prefix sums keep_offset [n],
+ * append_offset [n] and counts[2] = {n_keep, n_append} (device memory).  scratch: grut_relayout_scratch_bytes(n) bytes, 16-byte
+ * aligned like the offsets. */
+int grut_relayout_scan(void* stream, uint32_t n, const uint8_t* keep, const uint8_t* append, uint32_t* keep_offset,
+                       uint32_t* append_offset, uint32_t* counts, void* scratch, uint64_t scratch_bytes);
+uint64_t grut_relayout_scratch_bytes(uint32_t n);
+/* Replaces torch.cat([v[keep], v[append].repeat(copies, 1)]) of one tensor (the update_param_fn / update_optimizer_fn closures of
+ * gs.py:179-196, :218-223, :236-240, :258-262, :276-280 as applied by strategy/base.py:76-107): in [n, row_elems] of 4-byte elements
+ * (copied as bits) -> out [n_keep + copies n_append, row_elems].  Kept row i lands at keep_offset[i]; copy c of appended row i at
+ * n_keep + c n_append + append_offset[i] (the whole block repeated), zeros instead with GRUT_APPEND_ZERO.  Masks, offsets and counts
+ * are those of grut_relayout_scan; an output of zero rows launches nothing. */
+int grut_relayout_rows(void* stream, uint32_t n, uint32_t row_elems, const void* in, const uint8_t* keep, const uint8_t* append,
+                       const uint32_t* keep_offset, const uint32_t* append_offset, uint32_t n_keep, uint32_t n_append,
+                       uint32_t copies, int append_mode, void* out);
+/* Finishes the appended block of a split (gs.py:168-186, exp scale activation) IN PLACE over its n = copies n_append rows, given the
+ * tails of the new raw tensors: positions += R(q / |q|) (noise * exp(scale)) with R of quaternion_to_so3 (utils/misc.py:67-88,
+ * q = (w, x, y, z) from rotation_tail [n,4]) and noise [n,3] standard normals; then scale = log(exp(scale) / (0.8 copies)): exp in
+ * fp32, the quotient and its logarithm in fp64 rounded once (closer to the exact value than the reference's all-fp32 chain, not
+ * bit-identical to it). */
+int grut_split_tail(void* stream, uint32_t n, float* positions_tail, float* scale_tail, const float* rotation_tail,
+                    const float* noise, uint32_t copies);
+
 /* ---- fused SSIM loss (the `fused_ssim` package as called by threedgrut/model/losses.py:31-33) ------------------- */
 /* Both entry points replace fused_ssim(img1, img2, padding) of the CUDA-only third-party extension the reference's loss imports
  * (threedgrut/model/losses.py:17; trainer.py:715-720 evaluates 1 - ssim on every step).  Window: separable 11-tap Gaussian, sigma 1.5,
