@@ -156,6 +156,7 @@ EXPORTED_SYMBOLS = [
     "grut_mcmc_relocation", "grut_mcmc_perturb",
     "grut_densify_accumulate", "grut_relayout_scan", "grut_relayout_scratch_bytes", "grut_relayout_rows", "grut_split_tail",
     "grut_ssim_forward", "grut_ssim_backward", "grut_ssim_partials",
+    "grut_photo_loss_forward", "grut_photo_loss_backward", "grut_photo_loss_partials",
     "grut_last_error", "grut_abi_version", "grut_set_allocator", "gut_trim", "grt_trim",
 ]
 
@@ -277,6 +278,14 @@ def _declare(lib):
     lib.grut_ssim_backward.restype = C.c_int
     lib.grut_ssim_partials.argtypes = [C.c_int] * 4
     lib.grut_ssim_partials.restype = C.c_uint32
+    # pred, its strides, gt, its strides, mask, its strides [3], terms, valid, then outputs / planes as for the SSIM pair
+    lib.grut_photo_loss_forward.argtypes = [vp] + [C.c_int] * 4 + [fp, strides, fp, strides, fp, strides, C.c_int, C.c_int, fp, fp, fp, fp, fp]
+    lib.grut_photo_loss_forward.restype = C.c_int
+    lib.grut_photo_loss_backward.argtypes = [vp] + [C.c_int] * 4 + [fp, strides, fp, strides, fp, strides, C.c_int, C.c_int, fp, fp, fp, fp, fp,
+                                                                    strides]
+    lib.grut_photo_loss_backward.restype = C.c_int
+    lib.grut_photo_loss_partials.argtypes = [C.c_int] * 4
+    lib.grut_photo_loss_partials.restype = C.c_uint32
     lib.grut_last_error.argtypes = []
     lib.grut_last_error.restype = C.c_char_p
     lib.grut_abi_version.argtypes = []

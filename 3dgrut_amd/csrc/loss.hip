@@ -369,3 +369,390 @@ extern "C" int grut_ssim_backward(void* stream, int B, int C, int H, int W, cons
     GRUT_HIP(hipGetLastError());
     return GRUT_OK;
 }
+
+// ---- fused photometric loss: mask, L1, L2 and SSIM in one pass each way (trainer.py:687-720) -----------------------------------
+//
+//   a = m pred, b = m gt (m = 1 without a mask: no multiply is issued)
+//   out = { mean|a - b|,  mean (pred - b)^2,  mean SSIM(a, b) }     (the L2 term's unmasked prediction is the reference's: trainer.py:709)
+//
+// Same tiling, staging and window sums as the SSIM kernels above, whose device helpers these share.  The mask ([B, H, W], broadcast over the
+// channels) is staged into LDS first, so it is read once per pixel; the images are multiplied by it on their way into LDS.  |a - b| and
+// (pred - b)^2 are added up by the lane that stages the element, for the 32x32 centre of the staged tile only, so every pixel is counted
+// by exactly one workgroup and no image word is read twice for them.  Per workgroup up to three partial sums leave in a fixed order
+// (partials[k * workgroups + workgroup], k = 0 L1, 1 L2, 2 SSIM); a one-workgroup launch adds them in fp64.  The backward adds
+// g_l1 m sign(a - b) / P and 2 g_l2 (pred - b) / P to the SSIM gradient at the centre pixel it already holds in LDS.  Terms that are not
+// selected cost nothing but the staging; with the SSIM term off the backward skips the window sums altogether.
+// LDS on top of the SSIM kernels' for a mask: 42x42 words forward (NC = 3: 74.5 KiB, still two workgroups per CU), 32x32 backward (64.4 KiB).
+namespace grut {
+
+constexpr int kPhotoL1 = 1, kPhotoL2 = 2, kPhotoSsim = 4, kPhotoTerms = 3;
+
+struct PhotoMask {   // [B, H, W] through element strides
+    const float* p;
+    long long sb, sh, sw;
+    __device__ __forceinline__ float at(int b, int y, int x) const { return p[b * sb + y * sh + x * sw]; }
+};
+
+template <int NC, bool TRAIN, bool MASKED>
+__global__ __launch_bounds__(kSsimThreads) __attribute__((amdgpu_waves_per_eu(1, 4))) void photo_forward_kernel(
+    SsimShape shp, SsimView img1, SsimView img2, PhotoMask mask, int terms, float* __restrict__ partials, float* __restrict__ dm_dmu1,
+    float* __restrict__ dm_ds1, float* __restrict__ dm_ds12) {
+    __shared__ float s_raw[2][NC][kSsimSpan][kSsimSpan];
+    __shared__ float s_h[5][kSsimSpan][kSsimTile];
+    __shared__ float s_m[MASKED ? kSsimSpan : 1][kSsimSpan];
+    __shared__ float s_red[kPhotoTerms][kSsimThreads / GRUT_WAVE];
+    const int t = threadIdx.x, H = shp.H, W = shp.W;
+    const int x0 = blockIdx.x * kSsimTile, y0 = blockIdx.y * kSsimTile;
+    const int groups = shp.C / NC, b = blockIdx.z / groups, c0 = (blockIdx.z % groups) * NC;
+
+    if constexpr (MASKED) {
+        ssim_stage<kSsimSpan * kSsimSpan, 1>(
+            t,
+            [&](int i) {
+                const int r = i / kSsimSpan, px = i - r * kSsimSpan;
+                const int y = y0 - kSsimHalo + r, x = x0 - kSsimHalo + px;
+                const bool in = y >= 0 && y < H && x >= 0 && x < W;
+                return SsimWords<1>{{in ? mask.at(b, y, x) : 0.0f}};
+            },
+            [&](int i, const SsimWords<1>& w) {
+                const int r = i / kSsimSpan, px = i - r * kSsimSpan;
+                s_m[r][px] = w.v[0];
+            });
+        __syncthreads();
+    }
+
+    float l1 = 0.0f, l2 = 0.0f;
+    constexpr int kRun = kSsimSpan * NC;   // one staged row as (pixel, channel) pairs: contiguous in channels-last memory
+    ssim_stage<kSsimSpan * kRun, 2>(
+        t,
+        [&](int i) {
+            const int r = i / kRun, j = i - r * kRun, px = j / NC, ch = j - px * NC;
+            const int y = y0 - kSsimHalo + r, x = x0 - kSsimHalo + px;
+            const bool in = y >= 0 && y < H && x >= 0 && x < W;
+            return SsimWords<2>{{in ? img1.at(b, c0 + ch, y, x) : 0.0f, in ? img2.at(b, c0 + ch, y, x) : 0.0f}};
+        },
+        [&](int i, const SsimWords<2>& w) {
+            const int r = i / kRun, j = i - r * kRun, px = j / NC, ch = j - px * NC;
+            float av = w.v[0], bv = w.v[1];
+            if constexpr (MASKED) {
+                const float m = s_m[r][px];
+                av *= m;
+                bv *= m;
+            }
+            s_raw[0][ch][r][px] = av;
+            s_raw[1][ch][r][px] = bv;
+            // the tile's own pixels (outside the image both words are 0): each belongs to exactly one workgroup
+            if (r >= kSsimHalo && r < kSsimHalo + kSsimTile && px >= kSsimHalo && px < kSsimHalo + kSsimTile) {
+                if (terms & kPhotoL1) l1 += fabsf(av - bv);
+                if (terms & kPhotoL2) {
+                    const float d = w.v[0] - bv;
+                    l2 = fmaf(d, d, l2);
+                }
+            }
+        });
+
+    const int x = t & (kSsimTile - 1), ys = (t / kSsimTile) * kSsimStrip;
+    float acc = 0.0f;
+    if (terms & kPhotoSsim) {
+        for (int ch = 0; ch < NC; ++ch) {
+            __syncthreads();   // the staged tile is complete / the previous channel's vertical pass has read s_h
+            for (int i = t; i < kSsimSpan * kSsimTile; i += kSsimThreads) {
+                const int r = i / kSsimTile, c = i & (kSsimTile - 1);
+                float m1 = 0.0f, m2 = 0.0f, xx = 0.0f, yy = 0.0f, xy = 0.0f;
+#pragma unroll
+                for (int k = 0; k < kSsimTaps; ++k) {
+                    const float p = s_raw[0][ch][r][c + k], q = s_raw[1][ch][r][c + k];
+                    const float wp = kSsimTap[k] * p, wq = kSsimTap[k] * q;
+                    m1 += wp;
+                    m2 += wq;
+                    xx = fmaf(wp, p, xx);
+                    yy = fmaf(wq, q, yy);
+                    xy = fmaf(wp, q, xy);
+                }
+                s_h[0][r][c] = m1;
+                s_h[1][r][c] = m2;
+                s_h[2][r][c] = xx;
+                s_h[3][r][c] = yy;
+                s_h[4][r][c] = xy;
+            }
+            __syncthreads();
+            float o[5][kSsimStrip];
+#pragma unroll
+            for (int q = 0; q < 5; ++q) ssim_vertical(s_h[q], ys, x, o[q]);
+#pragma unroll
+            for (int j = 0; j < kSsimStrip; ++j) {
+                const int gy = y0 + ys + j, gx = x0 + x;
+                if (gy >= H || gx >= W) continue;
+                const float mu1 = o[0][j], mu2 = o[1][j];
+                const float mu1s = mu1 * mu1, mu2s = mu2 * mu2, mu12 = mu1 * mu2;
+                const float s1 = o[2][j] - mu1s, s2 = o[3][j] - mu2s, s12 = o[4][j] - mu12;
+                const float a1 = 2.0f * mu12 + kSsimC1, a2 = 2.0f * s12 + kSsimC2;
+                const float b1 = mu1s + mu2s + kSsimC1, b2 = s1 + s2 + kSsimC2;
+                const float den = b1 * b2;
+                const float map = (a1 * a2) / den;
+                if (ssim_counted(shp, gy, gx)) acc += map;
+                if constexpr (TRAIN) {   // as ssim_forward_kernel: the planes are functions of a = m pred, the mask's factor is the backward's
+                    const float d_s1 = -map / b2;
+                    const float d_s12 = (2.0f * a1) / den;
+                    const float d_mu1 = (2.0f * a2) / den * (mu2 - mu1 * (a1 / b1)) - 2.0f * mu1 * d_s1 - mu2 * d_s12;
+                    const size_t at = (((size_t)b * shp.C + (c0 + ch)) * H + gy) * W + gx;
+                    dm_dmu1[at] = d_mu1;
+                    dm_ds1[at] = d_s1;
+                    dm_ds12[at] = d_s12;
+                }
+            }
+        }
+    }
+    l1 = wave_sum(l1);
+    l2 = wave_sum(l2);
+    acc = wave_sum(acc);
+    if ((t & (GRUT_WAVE - 1)) == 0) {
+        s_red[0][t / GRUT_WAVE] = l1;
+        s_red[1][t / GRUT_WAVE] = l2;
+        s_red[2][t / GRUT_WAVE] = acc;
+    }
+    __syncthreads();
+    if (t < kPhotoTerms && ((terms >> t) & 1)) {
+        float s = s_red[t][0];
+        for (int w = 1; w < kSsimThreads / GRUT_WAVE; ++w) s += s_red[t][w];
+        const uint32_t workgroups = gridDim.x * gridDim.y * gridDim.z;
+        partials[t * workgroups + (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// one workgroup, the three means one after the other, each as ssim_mean_kernel forms its one; a term that was not selected is written as 0
+__global__ __launch_bounds__(kSsimThreads) void photo_mean_kernel(const float* __restrict__ partials, uint32_t n, int terms, double inv_pixels,
+                                                                  double inv_ssim_count, float* __restrict__ out) {
+    __shared__ double s_sum[kSsimThreads];
+    for (int k = 0; k < kPhotoTerms; ++k) {
+        if (!((terms >> k) & 1)) {
+            if (threadIdx.x == 0) out[k] = 0.0f;
+            continue;
+        }
+        double s = 0.0;
+        for (uint32_t i = threadIdx.x; i < n; i += kSsimThreads) s += (double)partials[k * n + i];
+        __syncthreads();   // the previous term's tree has been read
+        s_sum[threadIdx.x] = s;
+        __syncthreads();
+        for (int half = kSsimThreads / 2; half > 0; half >>= 1) {
+            if ((int)threadIdx.x < half) s_sum[threadIdx.x] += s_sum[threadIdx.x + half];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) out[k] = (float)(s_sum[0] * (k == 2 ? inv_ssim_count : inv_pixels));
+    }
+}
+
+template <int NC, bool MASKED>
+__global__ __launch_bounds__(kSsimThreads) __attribute__((amdgpu_waves_per_eu(1, 4))) void photo_backward_kernel(
+    SsimShape shp, SsimView img1, SsimView img2, PhotoMask mask, int terms, const float* __restrict__ grad_out, float inv_count, double inv_pixels,
+    const float* __restrict__ dm_dmu1, const float* __restrict__ dm_ds1, const float* __restrict__ dm_ds12, float* __restrict__ grad,
+    long long gsb, long long gsc, long long gsh, long long gsw) {
+    __shared__ float s_x[kSsimTile][kSsimTile * NC], s_y[kSsimTile][kSsimTile * NC];   // pred (unmasked) and b = m gt, as in memory
+    __shared__ float s_m[MASKED ? kSsimTile : 1][kSsimTile];
+    __shared__ float s_p[3][kSsimSpan][kSsimSpan];
+    __shared__ float s_h[3][kSsimSpan][kSsimTile];
+    const int t = threadIdx.x, H = shp.H, W = shp.W;
+    const int x0 = blockIdx.x * kSsimTile, y0 = blockIdx.y * kSsimTile;
+    const int groups = shp.C / NC, b = blockIdx.z / groups, c0 = (blockIdx.z % groups) * NC;
+    const float scale = (terms & kPhotoSsim) ? grad_out[2] * inv_count : 0.0f;
+    const double c_l1 = (terms & kPhotoL1) ? (double)grad_out[0] * inv_pixels : 0.0;                  // rounded to fp32 once, after the mask
+    const float c_l2 = (terms & kPhotoL2) ? (float)(2.0 * (double)grad_out[1] * inv_pixels) : 0.0f;
+
+    if constexpr (MASKED) {
+        ssim_stage<kSsimTile * kSsimTile, 1>(
+            t,
+            [&](int i) {
+                const int r = i / kSsimTile, px = i - r * kSsimTile;
+                const int y = y0 + r, x = x0 + px;
+                return SsimWords<1>{{(y < H && x < W) ? mask.at(b, y, x) : 0.0f}};
+            },
+            [&](int i, const SsimWords<1>& w) { s_m[i / kSsimTile][i & (kSsimTile - 1)] = w.v[0]; });
+        __syncthreads();
+    }
+    constexpr int kRun = kSsimTile * NC;
+    ssim_stage<kSsimTile * kRun, 2>(
+        t,
+        [&](int i) {
+            const int r = i / kRun, j = i - r * kRun, px = j / NC, ch = j - px * NC;
+            const int y = y0 + r, x = x0 + px;
+            const bool in = y < H && x < W;
+            return SsimWords<2>{{in ? img1.at(b, c0 + ch, y, x) : 0.0f, in ? img2.at(b, c0 + ch, y, x) : 0.0f}};
+        },
+        [&](int i, const SsimWords<2>& w) {
+            const int r = i / kRun, j = i - r * kRun;
+            s_x[r][j] = w.v[0];
+            if constexpr (MASKED)
+                s_y[r][j] = s_m[r][j / NC] * w.v[1];
+            else
+                s_y[r][j] = w.v[1];
+        });
+
+    const int x = t & (kSsimTile - 1), ys = (t / kSsimTile) * kSsimStrip;
+    for (int ch = 0; ch < NC; ++ch) {
+        float o[3][kSsimStrip] = {};
+        if (terms & kPhotoSsim) {
+            __syncthreads();   // the previous channel's passes are done with s_p and s_h
+            const size_t plane = ((size_t)b * shp.C + (c0 + ch)) * H;
+            ssim_stage<kSsimSpan * kSsimSpan, 3>(
+                t,
+                [&](int i) {
+                    const int r = i / kSsimSpan, px = i - r * kSsimSpan;
+                    const int y = y0 - kSsimHalo + r, xg = x0 - kSsimHalo + px;
+                    const bool in = y >= 0 && xg >= 0 && ssim_counted(shp, y, xg);   // dL/dmap is 0 outside the counted region
+                    const size_t at = in ? (plane + y) * W + xg : 0;
+                    return SsimWords<3>{{in ? dm_dmu1[at] : 0.0f, in ? dm_ds1[at] : 0.0f, in ? dm_ds12[at] : 0.0f}};
+                },
+                [&](int i, const SsimWords<3>& w) {
+                    const int r = i / kSsimSpan, px = i - r * kSsimSpan;
+                    s_p[0][r][px] = w.v[0];
+                    s_p[1][r][px] = w.v[1];
+                    s_p[2][r][px] = w.v[2];
+                });
+            __syncthreads();
+            for (int i = t; i < kSsimSpan * kSsimTile; i += kSsimThreads) {
+                const int r = i / kSsimTile, c = i & (kSsimTile - 1);
+                float h0 = 0.0f, h1 = 0.0f, h2 = 0.0f;
+#pragma unroll
+                for (int k = 0; k < kSsimTaps; ++k) {
+                    h0 = fmaf(kSsimTap[k], s_p[0][r][c + k], h0);
+                    h1 = fmaf(kSsimTap[k], s_p[1][r][c + k], h1);
+                    h2 = fmaf(kSsimTap[k], s_p[2][r][c + k], h2);
+                }
+                s_h[0][r][c] = h0;
+                s_h[1][r][c] = h1;
+                s_h[2][r][c] = h2;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < 3; ++q) ssim_vertical(s_h[q], ys, x, o[q]);
+        } else if (ch == 0) {
+            __syncthreads();   // s_x and s_y are complete
+        }
+#pragma unroll
+        for (int j = 0; j < kSsimStrip; ++j) {   // each (row, pixel, channel) slot of s_x is read and overwritten by this lane alone
+            const float pv = s_x[ys + j][x * NC + ch], yv = s_y[ys + j][x * NC + ch];
+            float m = 1.0f, xv = pv;
+            if constexpr (MASKED) {
+                m = s_m[ys + j][x];
+                xv = m * pv;
+            }
+            float g = 0.0f;
+            if (terms & kPhotoSsim) {
+                g = scale * (o[0][j] + 2.0f * xv * o[1][j] + yv * o[2][j]);
+                if constexpr (MASKED) g *= m;
+            }
+            if (terms & kPhotoL1) {   // sign(0) = 0, as torch.abs's gradient
+                const float d = xv - yv;
+                const float sgn = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
+                if constexpr (MASKED)
+                    g += (float)((double)(m * sgn) * c_l1);
+                else
+                    g += sgn * (float)c_l1;
+            }
+            if (terms & kPhotoL2) g = fmaf(c_l2, pv - yv, g);
+            s_x[ys + j][x * NC + ch] = g;
+        }
+    }
+    __syncthreads();
+    for (int i = t; i < kSsimTile * kRun; i += kSsimThreads) {
+        const int r = i / kRun, j = i - r * kRun, px = j / NC, ch = j - px * NC;
+        const int y = y0 + r, xg = x0 + px;
+        if (y < H && xg < W) grad[b * gsb + (c0 + ch) * gsc + y * gsh + xg * gsw] = s_x[r][j];
+    }
+}
+
+static int photo_check(const char* who, int B, int C, int H, int W, int terms, int valid) {
+    GRUT_REQUIRE(terms >= 1 && terms <= (kPhotoL1 | kPhotoL2 | kPhotoSsim), "%s: terms must be a non-empty combination of 1 (L1), 2 (L2), 4 (SSIM) (got %d)",
+                 who, terms);
+    GRUT_REQUIRE(valid == 0 || valid == 1, "%s: valid must be 0 (\"same\") or 1 (got %d)", who, valid);
+    return ssim_check_shape(who, B, C, H, W, (terms & kPhotoSsim) ? valid : 0);   // the window's size limit only binds the SSIM term
+}
+
+template <int NC, bool MASKED>
+static void photo_launch_forward(bool train, dim3 grid, hipStream_t s, SsimShape shp, SsimView v1, SsimView v2, PhotoMask m, int terms,
+                                 float* partials, float* dm_dmu1, float* dm_ds1, float* dm_ds12) {
+    if (train)
+        hipLaunchKernelGGL((photo_forward_kernel<NC, true, MASKED>), grid, dim3(kSsimThreads), 0, s, shp, v1, v2, m, terms, partials, dm_dmu1,
+                           dm_ds1, dm_ds12);
+    else
+        hipLaunchKernelGGL((photo_forward_kernel<NC, false, MASKED>), grid, dim3(kSsimThreads), 0, s, shp, v1, v2, m, terms, partials,
+                           (float*)nullptr, (float*)nullptr, (float*)nullptr);
+}
+
+}  // namespace grut
+
+extern "C" uint32_t grut_photo_loss_partials(int B, int C, int H, int W) { return grut::kPhotoTerms * grut_ssim_partials(B, C, H, W); }
+
+extern "C" int grut_photo_loss_forward(void* stream, int B, int C, int H, int W, const float* pred, const int64_t* pred_stride, const float* gt,
+                                       const int64_t* gt_stride, const float* mask, const int64_t* mask_stride, int terms, int valid,
+                                       float* out, float* partials, float* dm_dmu1, float* dm_ds1, float* dm_ds12) {
+    using namespace grut;
+    GRUT_CHECK(photo_check("grut_photo_loss_forward", B, C, H, W, terms, valid));
+    GRUT_REQUIRE(pred && gt && pred_stride && gt_stride && out && partials, "grut_photo_loss_forward: null tensor");
+    GRUT_REQUIRE(!mask || mask_stride, "grut_photo_loss_forward: a mask needs its strides");
+    const bool train = dm_dmu1 || dm_ds1 || dm_ds12;
+    GRUT_REQUIRE(!train || (dm_dmu1 && dm_ds1 && dm_ds12), "grut_photo_loss_forward: the three derivative planes are given together or not at all");
+    GRUT_REQUIRE(!train || (terms & kPhotoSsim), "grut_photo_loss_forward: derivative planes are only written with the SSIM term (4) selected");
+    const int nc = std::min(ssim_channels_per_group(C, W, pred_stride), ssim_channels_per_group(C, W, gt_stride));
+    const dim3 grid = ssim_grid(B, C, H, W, nc);
+    const SsimShape shp{C, H, W, valid};
+    const SsimView v1{pred, pred_stride[0], pred_stride[1], pred_stride[2], pred_stride[3]}, v2{gt, gt_stride[0], gt_stride[1], gt_stride[2], gt_stride[3]};
+    const PhotoMask m = mask ? PhotoMask{mask, mask_stride[0], mask_stride[1], mask_stride[2]} : PhotoMask{nullptr, 0, 0, 0};
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+#define GRUT_PHOTO_FWD(NC)                                                                                    \
+    if (mask)                                                                                                 \
+        photo_launch_forward<NC, true>(train, grid, s, shp, v1, v2, m, terms, partials, dm_dmu1, dm_ds1, dm_ds12); \
+    else                                                                                                      \
+        photo_launch_forward<NC, false>(train, grid, s, shp, v1, v2, m, terms, partials, dm_dmu1, dm_ds1, dm_ds12)
+    switch (nc) {
+        case 2: GRUT_PHOTO_FWD(2); break;
+        case 3: GRUT_PHOTO_FWD(3); break;
+        case 4: GRUT_PHOTO_FWD(4); break;
+        default: GRUT_PHOTO_FWD(1); break;
+    }
+#undef GRUT_PHOTO_FWD
+    GRUT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(photo_mean_kernel, dim3(1), dim3(kSsimThreads), 0, s, partials, grid.x * grid.y * grid.z, terms,
+                       1.0 / ((double)B * C * (double)H * (double)W), (terms & kPhotoSsim) ? 1.0 / ssim_count(B, C, H, W, valid) : 0.0, out);
+    GRUT_HIP(hipGetLastError());
+    return GRUT_OK;
+}
+
+extern "C" int grut_photo_loss_backward(void* stream, int B, int C, int H, int W, const float* pred, const int64_t* pred_stride, const float* gt,
+                                        const int64_t* gt_stride, const float* mask, const int64_t* mask_stride, int terms, int valid,
+                                        const float* grad_out, const float* dm_dmu1, const float* dm_ds1, const float* dm_ds12, float* grad_pred,
+                                        const int64_t* grad_stride) {
+    using namespace grut;
+    GRUT_CHECK(photo_check("grut_photo_loss_backward", B, C, H, W, terms, valid));
+    GRUT_REQUIRE(pred && gt && pred_stride && gt_stride && grad_out && grad_pred && grad_stride, "grut_photo_loss_backward: null tensor");
+    GRUT_REQUIRE(!mask || mask_stride, "grut_photo_loss_backward: a mask needs its strides");
+    GRUT_REQUIRE(!(terms & kPhotoSsim) || (dm_dmu1 && dm_ds1 && dm_ds12), "grut_photo_loss_backward: the SSIM term (4) needs the three derivative planes");
+    const int nc = std::min(std::min(ssim_channels_per_group(C, W, pred_stride), ssim_channels_per_group(C, W, gt_stride)),
+                            ssim_channels_per_group(C, W, grad_stride));
+    const dim3 grid = ssim_grid(B, C, H, W, nc);
+    const SsimShape shp{C, H, W, valid};
+    const SsimView v1{pred, pred_stride[0], pred_stride[1], pred_stride[2], pred_stride[3]}, v2{gt, gt_stride[0], gt_stride[1], gt_stride[2], gt_stride[3]};
+    const PhotoMask m = mask ? PhotoMask{mask, mask_stride[0], mask_stride[1], mask_stride[2]} : PhotoMask{nullptr, 0, 0, 0};
+    const float inv_count = (terms & kPhotoSsim) ? (float)(1.0 / ssim_count(B, C, H, W, valid)) : 0.0f;
+    const double inv_pixels = 1.0 / ((double)B * C * (double)H * (double)W);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+#define GRUT_PHOTO_BWD_M(NC, MASKED)                                                                                                         \
+    hipLaunchKernelGGL((photo_backward_kernel<NC, MASKED>), grid, dim3(kSsimThreads), 0, s, shp, v1, v2, m, terms, grad_out, inv_count, inv_pixels, \
+                       dm_dmu1, dm_ds1, dm_ds12, grad_pred, (long long)grad_stride[0], (long long)grad_stride[1], (long long)grad_stride[2],      \
+                       (long long)grad_stride[3])
+#define GRUT_PHOTO_BWD(NC)         \
+    if (mask)                      \
+        GRUT_PHOTO_BWD_M(NC, true); \
+    else                           \
+        GRUT_PHOTO_BWD_M(NC, false)
+    switch (nc) {
+        case 2: GRUT_PHOTO_BWD(2); break;
+        case 3: GRUT_PHOTO_BWD(3); break;
+        case 4: GRUT_PHOTO_BWD(4); break;
+        default: GRUT_PHOTO_BWD(1); break;
+    }
+#undef GRUT_PHOTO_BWD
+#undef GRUT_PHOTO_BWD_M
+    GRUT_HIP(hipGetLastError());
+    return GRUT_OK;
+}

@@ -598,6 +598,34 @@ int grut_ssim_backward(void* stream, int B, int C, int H, int W, const float* im
 /* How many floats of `partials` the forward call may write for this shape (one per workgroup; 0 for a bad shape). */
 uint32_t grut_ssim_partials(int B, int C, int H, int W);
 
+/* ---- fused photometric loss (threedgrut/trainer.py:687-720: mask, L1, L2 and SSIM of get_losses) ------------------- */
+/* One pass over both images each way for everything Trainer3DGRUT.get_losses takes from them.  With a = mask pred and b = mask gt
+ * (trainer.py:692-694; mask NULL: a = pred, b = gt):
+ *   out[0] = mean |a - b|                 torch.abs(rgb_pred - rgb_gt).mean()                            trainer.py:701
+ *   out[1] = mean (pred - b)^2            mse_loss(outputs["pred_features"], rgb_gt): UNMASKED pred      trainer.py:709
+ *   out[2] = mean SSIM(a, b)              ssim(permute(rgb_pred), permute(rgb_gt)), see grut_ssim_forward trainer.py:717-719
+ * terms selects what is computed: 1 (L1) | 2 (L2) | 4 (SSIM); out[k] of a term that is not selected is written as 0.  valid as for
+ * grut_ssim_forward (it only concerns the SSIM term, as does the H, W >= 11 limit).  pred / gt / grad_pred follow the strides contract of
+ * the SSIM entry points; mask is a [B, H, W] fp32 DEVICE tensor addressed through mask_stride[3] (element strides of B, H, W), broadcast
+ * over the channels and read once per pixel.  partials [grut_photo_loss_partials] and the three planes (B C H W floats each; all NULL for
+ * inference, and only allowed with the SSIM term selected) belong to the caller; nothing needs to be zeroed, no atomics, bitwise reproducible.
+ * With mask NULL and terms = 4, out[2] and the gradient are bit for bit those of grut_ssim_forward / grut_ssim_backward. */
+int grut_photo_loss_forward(void* stream, int B, int C, int H, int W, const float* pred, const int64_t* pred_stride, const float* gt,
+                            const int64_t* gt_stride, const float* mask, const int64_t* mask_stride, int terms, int valid, float* out,
+                            float* partials, float* dm_dmu1, float* dm_ds1, float* dm_ds12);
+/* The backward of all selected terms in one launch (replaces autograd's chain for trainer.py:693-720), grad_out [3] read from DEVICE
+ * memory (entries of terms that are not selected are not read), P = B C H W:
+ *   dL/dpred = mask [ G*(dL dm_dmu1) + 2 a G*(dL dm_ds1) + b G*(dL dm_ds12) ]   dL = grad_out[2] / count inside the counted region
+ *            + grad_out[0] mask sign(a - b) / P                                  sign(0) = 0
+ *            + 2 grad_out[1] (pred - b) / P
+ * grad_pred is fully written through grad_stride.  The planes are those the forward call wrote (NULL without the SSIM term). */
+int grut_photo_loss_backward(void* stream, int B, int C, int H, int W, const float* pred, const int64_t* pred_stride, const float* gt,
+                             const int64_t* gt_stride, const float* mask, const int64_t* mask_stride, int terms, int valid,
+                             const float* grad_out, const float* dm_dmu1, const float* dm_ds1, const float* dm_ds12, float* grad_pred,
+                             const int64_t* grad_stride);
+/* How many floats of `partials` the forward call may write for this shape (three per workgroup; 0 for a bad shape). */
+uint32_t grut_photo_loss_partials(int B, int C, int H, int W);
+
 /* ---- optimizer step --------------------------------------- */
 /* One parameter group of SelectiveAdam (threedgrut/optimizers/__init__.py:85-124): contiguous fp32 [num_rows, row_width]
  * DEVICE tensors, 16-byte aligned. */
