@@ -157,6 +157,7 @@ EXPORTED_SYMBOLS = [
     "grut_densify_accumulate", "grut_relayout_scan", "grut_relayout_scratch_bytes", "grut_relayout_rows", "grut_split_tail",
     "grut_ssim_forward", "grut_ssim_backward", "grut_ssim_partials",
     "grut_photo_loss_forward", "grut_photo_loss_backward", "grut_photo_loss_partials",
+    "grut_knn", "grut_knn_scratch_bytes",
     "grut_last_error", "grut_abi_version", "grut_set_allocator", "gut_trim", "grt_trim",
 ]
 
@@ -286,6 +287,11 @@ def _declare(lib):
     lib.grut_photo_loss_backward.restype = C.c_int
     lib.grut_photo_loss_partials.argtypes = [C.c_int] * 4
     lib.grut_photo_loss_partials.restype = C.c_uint32
+    # stream, num_points, points, num_queries, queries (NULL: self query), k, exclude_self, out_dist, out_index, scratch, its bytes, out_nonfinite
+    lib.grut_knn.argtypes = [vp, C.c_uint32, fp, C.c_uint32, fp, C.c_int, C.c_int, fp, ip, vp, C.c_size_t, up]
+    lib.grut_knn.restype = C.c_int
+    lib.grut_knn_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+    lib.grut_knn_scratch_bytes.restype = C.c_size_t
     lib.grut_last_error.argtypes = []
     lib.grut_last_error.restype = C.c_char_p
     lib.grut_abi_version.argtypes = []

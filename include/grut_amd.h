@@ -27,6 +27,7 @@
 #ifndef GRUT_AMD_H
 #define GRUT_AMD_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -625,6 +626,28 @@ int grut_photo_loss_backward(void* stream, int B, int C, int H, int W, const flo
                              const int64_t* grad_stride);
 /* How many floats of `partials` the forward call may write for this shape (three per workgroup; 0 for a bad shape). */
 uint32_t grut_photo_loss_partials(int B, int C, int H, int W);
+
+/* ---- nearest-neighbour initialisation (threedgrut/model/geometry.py) ----------------------------------------------- */
+/* Exact k nearest neighbours in 3-D, the device side of what the reference's initialisation takes from sklearn.neighbors:
+ * k_nearest_neighbors (geometry.py:42-49, called at model.py:732 for the Gaussians' initial size), nearest_neighbors (geometry.py:52-73)
+ * and nearest_neighbor_dist_cpuKD (geometry.py:76-117, called at model.py:588 and :728).  points [num_points,3] and queries
+ * [num_queries,3] are contiguous fp32 DEVICE tensors; queries = NULL (num_queries is then ignored): every point queries the set it
+ * belongs to.  1 <= k <= 16, num_points and num_queries < 2^31.
+ * Selection: the k points with the smallest fp32 key (dx dx + dy dy) + dz dz, dx = q.x - p.x rounded to fp32 (contracted or not), ties
+ * broken by the LOWER point index - a total order, so the result does not depend on the order in which the search visits the points and
+ * is bitwise reproducible.  exclude_self (only with queries = NULL) removes the query's own INDEX from its candidates (coincident other
+ * points remain).  Reported: out_dist [Q,k] in the order of the key (ascending; where two keys differ only by their rounding, the
+ * distances may be out of order by as little) (NULL: not wanted), for the selected points recomputed in double from the fp32
+ * coordinates and rounded once, (float)sqrt(dx dx + dy dy + dz dz) - the number sklearn's float64 search returns after the cast of
+ * geometry.py:49; out_index [Q,k] int32 original point indices in the same order (NULL: not wanted; not both NULL).
+ * out_nonfinite [1] (device) receives the number of NaN / inf coordinates among points and queries; when it is not 0 the outputs are
+ * unspecified (every access stays in bounds).  scratch: grut_knn_scratch_bytes(num_points, num_queries) bytes (num_queries = 0: self
+ * query), 16-byte aligned, contents arbitrary - nothing relies on zeroed scratch.  No allocation, no synchronisation, every launch on
+ * `stream`.  k > 16, k > num_points - exclude_self, exclude_self with queries, a missing pointer or a short scratch: GRUT_ERR_BAD_INPUT
+ * before anything is launched. */
+size_t grut_knn_scratch_bytes(uint32_t num_points, uint32_t num_queries);
+int grut_knn(void* stream, uint32_t num_points, const float* points, uint32_t num_queries, const float* queries, int k, int exclude_self,
+             float* out_dist, int32_t* out_index, void* scratch, size_t scratch_bytes, uint32_t* out_nonfinite);
 
 /* ---- optimizer step --------------------------------------- */
 /* One parameter group of SelectiveAdam (threedgrut/optimizers/__init__.py:85-124): contiguous fp32 [num_rows, row_width]
