@@ -45,9 +45,18 @@ def _strides(t):
     return (C.c_int64 * 4)(*t.stride())
 
 
-def _check_input(img1, img2, padding):
+def _plane_ptrs(planes):
+    """The three derivative planes of a [3, B, C, H, W] tensor as arguments, or three nulls."""
+    return [C.c_void_p(None)] * 3 if planes is None else [_ptr(planes[i]) for i in range(3)]
+
+
+def _check_padding(padding):
     if padding not in ("same", "valid"):
         raise ValueError(f"padding must be \"same\" or \"valid\" (got {padding!r})")
+
+
+def _check_input(img1, img2, padding):
+    _check_padding(padding)
     for t, name in ((img1, "img1"), (img2, "img2")):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a tensor")
@@ -83,6 +92,10 @@ def _readable_in_place(t):
     return True
 
 
+def _in_place(t):
+    return t if _readable_in_place(t) else t.contiguous()
+
+
 class _FusedSSIM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img1, img2, valid, train):
@@ -94,11 +107,10 @@ class _FusedSSIM(torch.autograd.Function):
         planes = torch.empty((3, b, c, h, w), **opts) if train else None
         stats["forward_calls"] += 1
         stats["planes_allocated"] += 3 if train else 0
-        null = C.c_void_p(None)
         with torch.cuda.device(img1.device):   # the launch goes to the images' device, whichever is current
             _abi.check(lib.grut_ssim_forward(
                 _stream(img1), b, c, h, w, _ptr(img1), _strides(img1), _ptr(img2), _strides(img2), valid, _ptr(out), _ptr(partials),
-                *([_ptr(planes[i]) for i in range(3)] if train else [null] * 3)), "grut_ssim_forward")
+                *_plane_ptrs(planes)), "grut_ssim_forward")
         if train:
             ctx.save_for_backward(img1, img2, planes)
             ctx.valid = valid
@@ -115,7 +127,7 @@ class _FusedSSIM(torch.autograd.Function):
         with torch.cuda.device(img1.device):
             _abi.check(_abi.load_library().grut_ssim_backward(
                 _stream(img1), b, c, h, w, _ptr(img1), _strides(img1), _ptr(img2), _strides(img2), ctx.valid, _ptr(grad_out),
-                _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2]), _ptr(grad), _strides(grad)), "grut_ssim_backward")
+                *_plane_ptrs(planes), _ptr(grad), _strides(grad)), "grut_ssim_backward")
         return grad, None, None, None
 
 
@@ -125,10 +137,7 @@ def fused_ssim(img1: torch.Tensor, img2: torch.Tensor, padding: str = "same", tr
     constant).  With train=False, under torch.no_grad() or when img1 does not require grad, only the value is computed and the three
     derivative planes are neither allocated nor written."""
     _check_input(img1, img2, padding)
-    if not _readable_in_place(img1):
-        img1 = img1.contiguous()
-    if not _readable_in_place(img2):
-        img2 = img2.contiguous()
+    img1, img2 = _in_place(img1), _in_place(img2)
     train = bool(train) and torch.is_grad_enabled() and img1.requires_grad
     if not train:
         img1 = img1.detach()
@@ -176,7 +185,7 @@ class _PhotometricLoss(torch.autograd.Function):
             _abi.check(lib.grut_photo_loss_forward(
                 _stream(pred), b, c, h, w, _ptr(pred), _strides(pred), _ptr(gt), _strides(gt),
                 null if mask is None else _ptr(mask), None if mask is None else _strides3(mask), terms, valid, _ptr(out), _ptr(partials),
-                *([null] * 3 if planes is None else [_ptr(planes[i]) for i in range(3)])), "grut_photo_loss_forward")
+                *_plane_ptrs(planes)), "grut_photo_loss_forward")
         if train:
             ctx.save_for_backward(*(t for t in (pred, gt, mask, planes) if t is not None))
             ctx.has_mask, ctx.terms, ctx.valid = mask is not None, terms, valid
@@ -205,7 +214,7 @@ class _PhotometricLoss(torch.autograd.Function):
             _abi.check(_abi.load_library().grut_photo_loss_backward(
                 _stream(pred), b, c, h, w, _ptr(pred), _strides(pred), _ptr(gt), _strides(gt),
                 null if mask is None else _ptr(mask), None if mask is None else _strides3(mask), ctx.terms, ctx.valid, _ptr(grad_out),
-                *([null] * 3 if planes is None else [_ptr(planes[i]) for i in range(3)]), _ptr(grad), _strides(grad)),
+                *_plane_ptrs(planes), _ptr(grad), _strides(grad)),
                 "grut_photo_loss_backward")
         return grad, None, None, None, None, None
 
@@ -248,16 +257,12 @@ def photometric_loss(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor | 
         if t.dim() != 4:
             raise RuntimeError(f"{name} must be {'[B, C, H, W]' if channels_first else '[B, H, W, C]'} (got {t.dim()} dimensions)")
     img1, img2 = (pred, gt) if channels_first else (pred.permute(0, 3, 1, 2), gt.permute(0, 3, 1, 2))
-    if padding not in ("same", "valid"):
-        raise ValueError(f"padding must be \"same\" or \"valid\" (got {padding!r})")
+    _check_padding(padding)
     _check_input(img1, img2, padding if ssim else "same")   # the window's size limit only binds the SSIM term
     b, _, h, w = (int(s) for s in img1.shape)
     if mask is not None:
         mask = _photo_mask(mask, b, h, w, img1.device, channels_first)
-    if not _readable_in_place(img1):
-        img1 = img1.contiguous()
-    if not _readable_in_place(img2):
-        img2 = img2.contiguous()
+    img1, img2 = _in_place(img1), _in_place(img2)
     train = torch.is_grad_enabled() and img1.requires_grad
     if not train:
         img1 = img1.detach()

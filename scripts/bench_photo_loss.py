@@ -5,7 +5,7 @@
   parent   what the commit before the fused call runs on every step: the formula of Trainer3DGRUT.get_losses (trainer.py:687-747) as a
            chain of torch kernels (mask products, abs / mean, the permuted views) around this repository's fused_ssim, and autograd's
            mirror image of it, including the kernel that adds the L1 and the SSIM gradient into pred.grad
-  fused    one photometric_loss call (csrc/loss.hip: photo_forward_kernel + photo_mean_kernel, photo_backward_kernel) and the same
+  fused    one photometric_loss call (csrc/loss.hip: loss_forward_kernel + loss_mean_kernel, loss_backward_kernel) and the same
            weighting of its three 0-dim results
 
 Both compute total = 0.8 l1 + 0.2 (1 - ssim) (the reference's default weights; L2 off, as in its configs) on channels-last RGB, the

@@ -1,4 +1,4 @@
-"""GPU: the fused photometric loss (photo_*_kernel of csrc/loss.hip through 3dgrut_amd.losses.photometric_loss) against a float64 torch
+"""GPU: the fused photometric loss (loss_*_kernel of csrc/loss.hip through 3dgrut_amd.losses.photometric_loss) against a float64 torch
 evaluation of what Trainer3DGRUT.get_losses takes from the two images (trainer.py:687-720), the SSIM part from tests/ssim_reference.py:
 
     a = m pred, b = m gt;   l1 = mean |a - b|;   l2 = mean (pred - b)^2  (the UNMASKED prediction: trainer.py:709);   ssim = mean SSIM(a, b)
@@ -19,7 +19,8 @@ The bounds treat a and b as exact.  They are when there is no mask or a binary o
 kernels see the same a and b.
 
 Shapes: 11x11 (one valid pixel), 37x45 (two tiles each way, neither a multiple of the 32x32 tile, inside the halo), 64x33 (an exact tile
-multiple down, one pixel over across), always B = 2; RGB channels-last as the renderer writes it and one planar channel.
+multiple down, one pixel over across), always B = 2; RGB channels-last as the renderer writes it and one planar channel.  The anchor
+test also takes planar RGB and channels-last images of 2 and 4 channels, so that every channels-per-workgroup instantiation (1..4) runs.
 Every test here needs `photometric_loss`, which the parent commit does not have."""
 import ctypes as C
 import functools
@@ -113,7 +114,7 @@ def _run(case, layout, weights=None, **terms):
 
 # ---- anchor: without a mask and with only the SSIM term, this IS fused_ssim -----------------------------------------------------------
 @pytest.mark.parametrize("padding", ["valid", "same"])
-@pytest.mark.parametrize("layout,c", LAYOUTS + [("nchw", 3)])
+@pytest.mark.parametrize("layout,c", LAYOUTS + [("nchw", 3), ("nhwc", 2), ("nhwc", 4)])   # NC = 3, 1, 1, 2, 4 channels per workgroup
 @pytest.mark.parametrize("h,w", SHAPES)
 def test_ssim_term_alone_is_bitwise_fused_ssim(h, w, layout, c, padding):
     losses = _losses()
