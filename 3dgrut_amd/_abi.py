@@ -158,6 +158,7 @@ EXPORTED_SYMBOLS = [
     "grut_ssim_forward", "grut_ssim_backward", "grut_ssim_partials",
     "grut_photo_loss_forward", "grut_photo_loss_backward", "grut_photo_loss_partials",
     "grut_knn", "grut_knn_scratch_bytes",
+    "grut_ppisp_forward", "grut_ppisp_backward", "grut_ppisp_partials",
     "grut_last_error", "grut_abi_version", "grut_set_allocator", "gut_trim", "grt_trim",
 ]
 
@@ -292,6 +293,14 @@ def _declare(lib):
     lib.grut_knn.restype = C.c_int
     lib.grut_knn_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
     lib.grut_knn_scratch_bytes.restype = C.c_size_t
+    # stream, num_pixels, rgb, pixel_coords, res_w, res_h, the four selected parameter rows (NULL: stage off), then out / grad_out, grad_rgb,
+    # the four parameter gradients (NULL: not wanted) and the partials
+    lib.grut_ppisp_forward.argtypes = [vp, C.c_uint32, fp, fp, C.c_float, C.c_float] + [fp] * 4 + [fp]
+    lib.grut_ppisp_forward.restype = C.c_int
+    lib.grut_ppisp_backward.argtypes = [vp, C.c_uint32, fp, fp, C.c_float, C.c_float] + [fp] * 4 + [fp] * 7
+    lib.grut_ppisp_backward.restype = C.c_int
+    lib.grut_ppisp_partials.argtypes = [C.c_uint32]
+    lib.grut_ppisp_partials.restype = C.c_uint32
     lib.grut_last_error.argtypes = []
     lib.grut_last_error.restype = C.c_char_p
     lib.grut_abi_version.argtypes = []

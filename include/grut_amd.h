@@ -627,6 +627,36 @@ int grut_photo_loss_backward(void* stream, int B, int C, int H, int W, const flo
 /* How many floats of `partials` the forward call may write for this shape (three per workgroup; 0 for a bad shape). */
 uint32_t grut_photo_loss_partials(int B, int C, int H, int W);
 
+/* ---- PPISP post-processing (threedgrut/utils/render.py:110-151, trainer.py:1166-1168) ---------------------------------- */
+/* The learned camera model the reference's trainer applies to every rendered frame before the loss (post_processing.method: ppisp), one
+ * pass over the image each way.  P pixels; rgb / out / grad_out / grad_rgb [P,3] and pixel_coords [P,2] (x, y with their +0.5) are
+ * contiguous fp32 DEVICE arrays; (res_w, res_h) is the image's resolution.  Stages, in order, with the ALREADY SELECTED parameter rows
+ * (the caller adds the frame's or camera's offset; nothing here reads an index or waits for the host):
+ *   exposure   [1]   x = rgb 2^e
+ *   vignetting [3,5] per channel (centre x, centre y, a1, a2, a3): uv = (pc - (W/2, H/2)) / max(W, H), r2 = |uv - centre|^2,
+ *                    x_c *= clamp(1 + a1 r2 + a2 r2^2 + a3 r2^3, 0, 1)
+ *   color      [8]   latents blue, red, green, neutral (two each) -> a 3x3 homography Hm; v = Hm (r, g, I) with I = r + g + b,
+ *                    v *= I / (v.z + 1e-5), rgb = (v.x, v.y, v.z - v.x - v.y)
+ *   crf        [3,4] per channel raw (toe, shoulder, gamma, centre): toe, shoulder = 0.3 + softplus, gamma = 0.1 + softplus,
+ *                    centre = clamp(sigmoid, 1e-6, 1 - 1e-6), l = max((shoulder - toe) centre + toe, 1e-6), a = shoulder centre / l,
+ *                    x = clamp(x, 0, 1), y = a (x / centre)^toe for x <= centre, else 1 - (1 - a) ((1 - x) / (1 - centre))^shoulder,
+ *                    out = max(y, 0)^gamma
+ * A NULL parameter pointer makes its stage the identity (all four NULL: out = rgb); its gradient pointer must then be NULL as well.
+ * pixel_coords may be NULL only when vignetting is NULL.
+ * The backward pass recomputes the forward from rgb (nothing is saved) and writes grad_rgb (NULL: not wanted) and the gradients of the
+ * four RAW parameter rows (each NULL or the row), with the chain rule through softplus, sigmoid and the homography construction done
+ * here; the rows of the cross product that gave the homography's scale are treated as fixed.  Conventions at the kinks:
+ *   vignetting clamp  gradient reaches the five parameters where 0 <= p <= 1, inclusive (p = 1 exactly at the zero initialisation)
+ *   response curve    a channel whose input to the curve is <= 0 or >= 1 passes no gradient, neither to rgb nor to its four parameters
+ * partials: grut_ppisp_partials(P) floats of scratch that belong to the caller; nothing has to be zeroed.  No atomics: two runs on the
+ * same input are bitwise equal.  No allocation, no synchronisation, every launch on `stream`. */
+uint32_t grut_ppisp_partials(uint32_t num_pixels);
+int grut_ppisp_forward(void* stream, uint32_t num_pixels, const float* rgb, const float* pixel_coords, float res_w, float res_h,
+                       const float* exposure, const float* color, const float* vignetting, const float* crf, float* out);
+int grut_ppisp_backward(void* stream, uint32_t num_pixels, const float* rgb, const float* pixel_coords, float res_w, float res_h,
+                        const float* exposure, const float* color, const float* vignetting, const float* crf, const float* grad_out,
+                        float* grad_rgb, float* grad_exposure, float* grad_color, float* grad_vignetting, float* grad_crf, float* partials);
+
 /* ---- nearest-neighbour initialisation (threedgrut/model/geometry.py) ----------------------------------------------- */
 /* Exact k nearest neighbours in 3-D, the device side of what the reference's initialisation takes from sklearn.neighbors:
  * k_nearest_neighbors (geometry.py:42-49, called at model.py:732 for the Gaussians' initial size), nearest_neighbors (geometry.py:52-73)

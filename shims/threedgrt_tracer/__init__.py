@@ -12,5 +12,7 @@ Tracer = _il.import_module("3dgrut_amd.grt_tracer").Tracer
 _il.import_module("3dgrut_amd.mcmc").install()
 # the loss's extension (threedgrut/model/losses.py:17 `from fused_ssim import fused_ssim`): the HIP fused SSIM unless one is installed
 _il.import_module("3dgrut_amd.losses").install()
+# the post-processing package (threedgrut/trainer.py:470 `from ppisp import PPISP, PPISPConfig`): the HIP PPISP unless one is installed
+_il.import_module("3dgrut_amd.ppisp").install()
 
 __all__ = ["Tracer"]
