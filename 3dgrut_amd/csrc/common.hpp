@@ -173,13 +173,15 @@ struct EventTimer {
 };
 
 // ---- scan / sort primitives (scan_sort.hip) -------------------------------------------------
-// inclusive scan of n u32; if gather != nullptr the input element i is in[gather[i]].
+// inclusive scan of n u32; if gather != nullptr the input element i is in[gather[i]].  `out` and (without gather) `in` are accessed
+// 16 bytes at a time and must be 16-byte aligned (GRUT_ERR_BAD_INPUT otherwise).
 size_t scan_scratch_bytes(uint32_t n);
 int inclusive_scan_u32(hipStream_t s, uint32_t n, const uint32_t* in, const uint32_t* gather, uint32_t* out,
                        void* scratch, size_t scratch_bytes);
 // stable LSD radix sort on key bits [begin_bit, end_bit); ping-pongs between (keys,vals) and (keys_tmp,vals_tmp),
 // *out_keys/*out_vals receive the buffers holding the sorted result.  `n_dev` (optional) points to the element
-// count in device memory (<= n); blocks beyond it exit early, so `n` may be a capacity bound.
+// count in device memory (<= n); blocks beyond it exit early, so `n` may be a capacity bound.  `keys` and `keys_tmp` are read 16 bytes
+// at a time and must be 16-byte aligned (GRUT_ERR_BAD_INPUT otherwise).
 size_t sort_scratch_bytes(uint32_t n);
 int sort_pairs_u32(hipStream_t s, uint32_t n, const uint32_t* n_dev, int begin_bit, int end_bit,
                    uint32_t* keys, uint32_t* vals, uint32_t* keys_tmp, uint32_t* vals_tmp,

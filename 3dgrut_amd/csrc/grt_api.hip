@@ -850,4 +850,12 @@ int grt_debug_fetch_lists(GrtHandle* h, void* stream_, uint32_t* ranges, uint32_
     return GRUT_OK;
 }
 
+int grt_debug_list_ranges(void* stream_, uint32_t n, const uint32_t* n_dev, uint32_t num_blocks, const uint32_t* sorted_keys, uint32_t* ranges) {
+    GRUT_REQUIRE(sorted_keys && ranges, "grt_debug_list_ranges: null argument");
+    GRUT_REQUIRE(((uintptr_t)sorted_keys & 15) == 0, "grt_debug_list_ranges: sorted_keys must be 16-byte aligned");
+    grt_launch_list_ranges(reinterpret_cast<hipStream_t>(stream_), n, n_dev, num_blocks, sorted_keys, ranges);
+    GRUT_HIP(hipGetLastError());
+    return GRUT_OK;
+}
+
 }  // extern "C"

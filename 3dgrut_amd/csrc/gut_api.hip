@@ -787,4 +787,15 @@ int gut_debug_fetch(GutHandle* h, void* stream_, uint32_t* tiles_count, float* p
     return GRUT_OK;
 }
 
+int gut_debug_tile_ranges(void* stream_, uint32_t n, const uint32_t* n_dev, uint32_t tile_mask, uint32_t num_tiles, const uint32_t* sorted_tile_keys,
+                          uint32_t* ranges, uint32_t* boundary_tile, uint32_t* segment) {
+    GRUT_REQUIRE(sorted_tile_keys && ranges && boundary_tile && segment, "gut_debug_tile_ranges: null argument");
+    GRUT_REQUIRE(((uintptr_t)sorted_tile_keys & 15) == 0, "gut_debug_tile_ranges: sorted_tile_keys must be 16-byte aligned");
+    *segment = kGutSegment;
+    if (n == 0) return GRUT_OK;
+    launch_tile_ranges(reinterpret_cast<hipStream_t>(stream_), n, n_dev, tile_mask, num_tiles, sorted_tile_keys, ranges, boundary_tile);
+    GRUT_HIP(hipGetLastError());
+    return GRUT_OK;
+}
+
 }  // extern "C"

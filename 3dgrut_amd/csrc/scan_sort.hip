@@ -99,7 +99,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_block_sums_kernel(uint32_t*
 
 // FUSED: block_sums holds the raw per-block totals and every block adds up the ones in front of it itself (a few loads per thread for
 // the array sizes of this path) — the single-block scan of the totals and its launch are skipped
-template <bool EXCLUSIVE, bool FUSED>
+template <bool FUSED>
 __global__ __launch_bounds__(kScanThreads) void scan_apply_kernel(const uint32_t* __restrict__ in,
                                                                   const uint32_t* __restrict__ gather, uint32_t n,
                                                                   const uint32_t* __restrict__ block_sums,
@@ -125,8 +125,8 @@ __global__ __launch_bounds__(kScanThreads) void scan_apply_kernel(const uint32_t
     uint32_t y[kScanItems];
 #pragma unroll
     for (int k = 0; k < kScanItems; ++k) {
-        if (EXCLUSIVE) { y[k] = run; run += x[k]; }
-        else { run += x[k]; y[k] = run; }
+        run += x[k];
+        y[k] = run;
     }
     if (i0 + kScanItems <= n) {
         *reinterpret_cast<uint4*>(out + i0)     = make_uint4(y[0], y[1], y[2], y[3]);
@@ -138,22 +138,20 @@ __global__ __launch_bounds__(kScanThreads) void scan_apply_kernel(const uint32_t
     }
 }
 
-int scan_impl(hipStream_t s, uint32_t n, const uint32_t* in, const uint32_t* gather, uint32_t* out, bool exclusive,
-              void* scratch, size_t scratch_bytes) {
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+int scan_impl(hipStream_t s, uint32_t n, const uint32_t* in, const uint32_t* gather, uint32_t* out, void* scratch, size_t scratch_bytes) {
     if (n == 0) return GRUT_OK;
+    // 16-byte accesses: the stores to out always, the loads from in unless they go through gather
+    GRUT_REQUIRE(aligned16(out) && (gather || aligned16(in)), "scan: in (without gather) and out must be 16-byte aligned");
     const uint32_t nb = div_up(n, kScanTile);
     GRUT_REQUIRE(scratch_bytes >= (size_t)nb * sizeof(uint32_t), "scan scratch too small");
     uint32_t* sums = reinterpret_cast<uint32_t*>(scratch);
     hipLaunchKernelGGL(scan_reduce_kernel, dim3(nb), dim3(kScanThreads), 0, s, in, gather, n, sums);
     const bool fused = nb <= 8192u;   // (<= 32 loads per thread for the prefix of the block totals)
     if (!fused) hipLaunchKernelGGL(scan_block_sums_kernel, dim3(1), dim3(kScanThreads), 0, s, sums, nb);
-    if (exclusive) {
-        if (fused) hipLaunchKernelGGL((scan_apply_kernel<true, true>), dim3(nb), dim3(kScanThreads), 0, s, in, gather, n, sums, out);
-        else hipLaunchKernelGGL((scan_apply_kernel<true, false>), dim3(nb), dim3(kScanThreads), 0, s, in, gather, n, sums, out);
-    } else {
-        if (fused) hipLaunchKernelGGL((scan_apply_kernel<false, true>), dim3(nb), dim3(kScanThreads), 0, s, in, gather, n, sums, out);
-        else hipLaunchKernelGGL((scan_apply_kernel<false, false>), dim3(nb), dim3(kScanThreads), 0, s, in, gather, n, sums, out);
-    }
+    if (fused) hipLaunchKernelGGL(scan_apply_kernel<true>, dim3(nb), dim3(kScanThreads), 0, s, in, gather, n, sums, out);
+    else hipLaunchKernelGGL(scan_apply_kernel<false>, dim3(nb), dim3(kScanThreads), 0, s, in, gather, n, sums, out);
     GRUT_HIP(hipGetLastError());
     return GRUT_OK;
 }
@@ -510,7 +508,7 @@ size_t scan_scratch_bytes(uint32_t n) { return (size_t)(div_up(n, kScanTile) + 1
 
 int inclusive_scan_u32(hipStream_t s, uint32_t n, const uint32_t* in, const uint32_t* gather, uint32_t* out,
                        void* scratch, size_t scratch_bytes) {
-    return scan_impl(s, n, in, gather, out, false, scratch, scratch_bytes);
+    return scan_impl(s, n, in, gather, out, scratch, scratch_bytes);
 }
 
 // one-sweep layout of the scratch: [kMaxPasses][kRadix] digit totals | kMaxPasses tickets (+ padding to 64 words) | [passes][tiles][kRadix] status words
@@ -542,6 +540,8 @@ int sort_pairs_u32(hipStream_t s, uint32_t n, const uint32_t* n_dev, int begin_b
     *out_vals = vals;
     if (n == 0 || end_bit <= begin_bit) return GRUT_OK;
     GRUT_REQUIRE(scratch_bytes >= sort_scratch_bytes(n), "sort scratch too small");
+    // (the histogram kernels read whichever buffer holds a pass's input 16 bytes at a time)
+    GRUT_REQUIRE(aligned16(keys) && aligned16(keys_tmp), "sort: keys and keys_tmp must be 16-byte aligned");
     const bool small = n <= kSortSmallLimit;
     const uint32_t nb = div_up(n, (uint32_t)(kSortThreads * (small ? kSortRoundsSmall : kSortRoundsLarge)));
     uint32_t* hist = reinterpret_cast<uint32_t*>(scratch);
@@ -612,6 +612,18 @@ int grut_sort_pairs_u32(void* stream, uint32_t n, int begin_bit, int end_bit, ui
 
 int grut_inclusive_scan_u32(void* stream, uint32_t n, const uint32_t* in, uint32_t* out, void* scratch, uint64_t scratch_bytes) {
     return grut::inclusive_scan_u32(reinterpret_cast<hipStream_t>(stream), n, in, nullptr, out, scratch, scratch_bytes);
+}
+
+int grut_debug_sort_pairs_u32(void* stream, uint32_t n, const uint32_t* n_dev, int begin_bit, int end_bit, uint32_t* keys, uint32_t* values,
+                              uint32_t* keys_tmp, uint32_t* values_tmp, int values_iota, void* scratch, uint64_t scratch_bytes,
+                              uint32_t** sorted_keys, uint32_t** sorted_values) {
+    return grut::sort_pairs_u32(reinterpret_cast<hipStream_t>(stream), n, n_dev, begin_bit, end_bit, keys, values, keys_tmp, values_tmp,
+                                scratch, scratch_bytes, sorted_keys, sorted_values, values_iota != 0);
+}
+
+int grut_debug_scan_gather_u32(void* stream, uint32_t n, const uint32_t* in, const uint32_t* gather, uint32_t* out, void* scratch,
+                               uint64_t scratch_bytes) {
+    return grut::inclusive_scan_u32(reinterpret_cast<hipStream_t>(stream), n, in, gather, out, scratch, scratch_bytes);
 }
 
 }  // extern "C"

@@ -265,17 +265,36 @@ int gut_profile_select(GutHandle* handle, uint32_t stage_mask);
 int gut_profile_read(GutHandle* handle, float* stage_ms /* [GUT_NUM_STAGES] */);
 
 /* ---- stage-level entry points (parity tests drive each stage alone) ------ */
-/* Stable LSD radix sort of (key,value) pairs on key bits [begin_bit,end_bit). tmp buffers sized n. */
+/* Stable LSD radix sort of (key,value) pairs on key bits [begin_bit,end_bit). tmp buffers sized n.
+ * keys and keys_tmp must be 16-byte aligned (the passes read them 16 bytes at a time); a misaligned pointer is GRUT_ERR_BAD_INPUT and
+ * nothing is launched. */
 int grut_sort_pairs_u32(void* stream, uint32_t n, int begin_bit, int end_bit,
                         uint32_t* keys, uint32_t* values,
                         uint32_t* keys_tmp, uint32_t* values_tmp,
                         void* scratch, uint64_t scratch_bytes,
                         uint32_t** sorted_keys, uint32_t** sorted_values);
 uint64_t grut_sort_scratch_bytes(uint32_t n);
-/* inclusive prefix sum of n u32 (cub::DeviceScan::InclusiveSum, gutRenderer.cu:302-310) */
+/* inclusive prefix sum of n u32 (cub::DeviceScan::InclusiveSum, gutRenderer.cu:302-310); in and out must be 16-byte aligned
+ * (GRUT_ERR_BAD_INPUT otherwise, nothing launched) */
 int grut_inclusive_scan_u32(void* stream, uint32_t n, const uint32_t* in, uint32_t* out,
                             void* scratch, uint64_t scratch_bytes);
 uint64_t grut_scan_scratch_bytes(uint32_t n);
+/* The same two primitives with the arguments the renderers vary.
+ * Sort: n_dev (DEVICE pointer, may be NULL) holds the live count, clamped to n - only the first min(*n_dev, n) pairs are read and
+ * written, n is then the capacity of the buffers; values_iota != 0: the payload of pair i is i, generated by the first pass - `values`
+ * is never read but still serves as a ping-pong buffer.  Same alignment rule.
+ * Scan: gather (DEVICE pointer, may be NULL): element i of the input is in[gather[i]]; `in` may then have any alignment, out not. */
+int grut_debug_sort_pairs_u32(void* stream, uint32_t n, const uint32_t* n_dev, int begin_bit, int end_bit,
+                              uint32_t* keys, uint32_t* values, uint32_t* keys_tmp, uint32_t* values_tmp, int values_iota,
+                              void* scratch, uint64_t scratch_bytes, uint32_t** sorted_keys, uint32_t** sorted_values);
+int grut_debug_scan_gather_u32(void* stream, uint32_t n, const uint32_t* in, const uint32_t* gather, uint32_t* out,
+                               void* scratch, uint64_t scratch_bytes);
+/* Tile ranges of a 3DGUT frame from its sorted tile keys (16-byte aligned) alone: ranges[t] = [first, last) of the entries whose
+ * key & tile_mask is t < num_tiles (tiles without entries are NOT written: clear the table first), boundary_tile[b] = the tile of entry
+ * b * *segment (0xFFFFFFFF where that entry's tile is >= num_tiles) for every such entry below the live count min(*n_dev, n) (n alone
+ * with n_dev NULL).  *segment (HOST) receives the library's segment length. */
+int gut_debug_tile_ranges(void* stream, uint32_t n, const uint32_t* n_dev, uint32_t tile_mask, uint32_t num_tiles,
+                          const uint32_t* sorted_tile_keys, uint32_t* ranges, uint32_t* boundary_tile, uint32_t* segment);
 
 /* Copies the binning products of the last gut_forward to caller DEVICE buffers (any may be NULL):
  * tiles_count[N] u32, proj_pos[N,2], conic_opacity[N,4], extent[N,2], depth[N], rgb[N,3],
@@ -497,6 +516,10 @@ int grt_debug_fetch_custom_boxes(GrtHandle* handle, void* stream, float* box8);
  * ([first, last) of each 8x8 ray packet, row-major), entries [list_entries] particle ids (top bit: internal flag).  GRUT_ERR_NOT_READY when
  * the tree walk served the frame or the capacity is too small.  The parity tests hand them to the CPU checker as a candidate prefilter. */
 int grt_debug_fetch_lists(GrtHandle* handle, void* stream, uint32_t* ranges, uint32_t* entries, uint64_t entry_capacity);
+/* Packet ranges from sorted block keys (16-byte aligned) alone: ranges[2 k], ranges[2 k + 1] = [first, last) of the entries whose key is
+ * k < num_blocks (blocks without entries are not written), over the first min(*n_dev, n) entries (n alone with n_dev NULL). */
+int grt_debug_list_ranges(void* stream, uint32_t n, const uint32_t* n_dev, uint32_t num_blocks, const uint32_t* sorted_keys,
+                          uint32_t* ranges);
 
 int grt_timings(GrtHandle* handle, float* forward_ms, float* backward_ms, float* build_ms);
 int grt_stats(GrtHandle* handle, GrtStats* stats);
