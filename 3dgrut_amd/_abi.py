@@ -144,6 +144,15 @@ class GutGradIO(C.Structure):
     _fields_ = [("grad_features", C.c_void_p), ("grad_opacity", C.c_void_p), ("grad_positions", C.c_void_p), ("grad_density", C.c_void_p),
                 ("grad_rotation", C.c_void_p), ("grad_scale", C.c_void_p)]
 
+MLP_ACT_NONE, MLP_ACT_RELU, MLP_ACT_SIGMOID = range(3)
+
+
+class GrutMlpConfig(C.Structure):
+    """include/grut_amd.h: GrutMlpConfig (the NHT decoder's network, grut_mlp_forward)."""
+    _fields_ = [("n_features", C.c_int32), ("sh_degree", C.c_int32), ("n_hidden_layers", C.c_int32), ("width", C.c_int32),
+                ("n_output_dims", C.c_int32), ("output_activation", C.c_int32)]
+
+
 # every symbol include/grut_amd.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = [
     "gut_create", "gut_destroy", "gut_forward", "gut_backward", "gut_backward_unpacked", "gut_backward_factored", "gut_backward_factored_chunked", "grut_sph_grad_from_views", "gut_timings", "gut_stats",
@@ -159,6 +168,7 @@ EXPORTED_SYMBOLS = [
     "grut_photo_loss_forward", "grut_photo_loss_backward", "grut_photo_loss_partials",
     "grut_knn", "grut_knn_scratch_bytes",
     "grut_ppisp_forward", "grut_ppisp_backward", "grut_ppisp_partials",
+    "grut_mlp_forward", "grut_mlp_lds_bytes", "grut_mlp_num_params",
     "grut_last_error", "grut_abi_version", "grut_set_allocator", "gut_trim", "grt_trim",
 ]
 
@@ -312,6 +322,13 @@ def _declare(lib):
     lib.grut_ppisp_backward.restype = C.c_int
     lib.grut_ppisp_partials.argtypes = [C.c_uint32]
     lib.grut_ppisp_partials.restype = C.c_uint32
+    # stream, config, params, input [P, F + 3], num_pixels, out [P, n_output_dims]
+    lib.grut_mlp_forward.argtypes = [vp, C.POINTER(GrutMlpConfig), fp, fp, C.c_uint32, fp]
+    lib.grut_mlp_forward.restype = C.c_int
+    lib.grut_mlp_lds_bytes.argtypes = [C.POINTER(GrutMlpConfig)]
+    lib.grut_mlp_lds_bytes.restype = C.c_uint32
+    lib.grut_mlp_num_params.argtypes = [C.POINTER(GrutMlpConfig)]
+    lib.grut_mlp_num_params.restype = C.c_uint32
     lib.grut_last_error.argtypes = []
     lib.grut_last_error.restype = C.c_char_p
     lib.grut_abi_version.argtypes = []

@@ -1,0 +1,255 @@
+// mlp.hip — the NHT decoder's network (threedgrut/model/feature_decoder.py: tinycudann's NetworkWithInputEncoding) as ONE fused HIP
+// forward kernel: encoding, every layer and the output activation, with nothing but the input row and the output row in memory.
+// The model: grut_mlp_forward in include/grut_amd.h.  Every index rule: mlp_layout.hpp (shared with the host emulation of the tests).
+//
+// Layout.  Persistent grid, one workgroup of four waves per CU (one wave per SIMD).  Each workgroup reads the fp32 `params` ITSELF,
+// rounds them to bf16 and writes the fragment-ordered image into LDS before its first tile: there is no prepared copy of the weights
+// anywhere, so a weight change of any kind (optimizer step, param.data.copy_ of the decoder's EMA) is seen by the next launch.
+// A wave then takes kColTiles tiles of 32 pixels per step.  Activations stay in registers, transposed ([neuron rows x 32 pixel columns]):
+// a layer is acc[m] = mfma_f32_32x32x16_bf16(W fragment (m, t) from LDS, H fragment t, acc[m]) over the row blocks m and k-steps t, and
+// its fp32 result, after ReLU and packed pairwise to bf16, IS the next layer's H operand (registers 8 s .. 8 s + 7 of row block b are
+// k-step 2 b + s).  One 16-byte LDS read per lane and fragment, lane-linear, shared by the kColTiles column tiles.
+// EXEC is all ones around every MFMA: a tail tile clamps its loads to the last pixel and masks its stores; nothing branches per lane.
+#include "common.hpp"
+#include "mlp_layout.hpp"
+
+namespace grut {
+namespace {
+
+using namespace grut_mlp;
+
+constexpr int kWavesPerBlock = 4, kBlock = kWavesPerBlock * GRUT_WAVE;
+constexpr int kColTiles = 2;   // column tiles (of 32 pixels) that share one weight fragment read: LDS bytes per pixel halve
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// two floats -> two bf16 (round to nearest even), low half first
+__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
+    const f32x2 v = {lo, hi};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+}
+__device__ __forceinline__ bf16x8 as_frag(uint4 v) { return __builtin_bit_cast(bf16x8, v); }
+
+// the 16 real SH polynomials of the contract for d = (x, y, z)
+__device__ __forceinline__ f32x16 sh_values(float x, float y, float z) {
+    const float xx = x * x, yy = y * y, zz = z * z;
+    f32x16 sh;
+    sh[0] = 0.28209479177387814f;
+    sh[1] = -0.48860251190291987f * y;
+    sh[2] = 0.48860251190291987f * z;
+    sh[3] = -0.48860251190291987f * x;
+    sh[4] = 1.0925484305920792f * (x * y);
+    sh[5] = -1.0925484305920792f * (y * z);
+    sh[6] = 0.94617469575755997f * zz - 0.31539156525251999f;
+    sh[7] = -1.0925484305920792f * (x * z);
+    sh[8] = 0.54627421529603959f * (xx - yy);
+    sh[9] = 0.59004358992664352f * (y * (-3.f * xx + yy));
+    sh[10] = 2.8906114426405538f * (x * y * z);
+    sh[11] = 0.45704579946446572f * (y * (1.f - 5.f * zz));
+    sh[12] = 0.3731763325901154f * (z * (5.f * zz - 3.f));
+    sh[13] = 0.45704579946446572f * (x * (1.f - 5.f * zz));
+    sh[14] = 1.4453057213202769f * (z * (xx - yy));
+    sh[15] = 0.59004358992664352f * (x * (-xx + 3.f * yy));
+    return sh;
+}
+
+// element e (mlp_input_element) of a pixel, e wave-uniform: an SH value or a one (a feature column gives an unused value)
+__device__ __forceinline__ float sh_or_one(int e, const f32x16& sh) {
+    const int i = -1 - e;                                  // the SH index; negative for a feature, huge for a one
+    float v = sh[__builtin_amdgcn_readfirstlane((i < 0 ? 0 : i) & 15)];   // a register picked by a SCALAR index: no lane ever differs
+    asm volatile("" : "+v"(v));                            // (keeps the pick from being merged with the other half's into a per-lane index)
+    return e == kInputOne ? 1.f : v;
+}
+
+// the B fragment of k-step t of the first layer: 8 elements of this lane's pixel, in the order of mlp_input_element.  Which kind of
+// element j is depends on the lane half only, so both halves' kinds are wave-uniform and the lane picks its own by h.
+__device__ __forceinline__ bf16x8 encode_step(const Shape& s, int t, int h, const float* __restrict__ row, const f32x16& sh) {
+    float v[8];
+    if (kStep * (t + 1) <= s.n_features) {   // (wave-uniform) all 16 elements are feature columns
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = row[mlp_input_element(s, t, h, j)];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int e0 = mlp_input_element(s, t, 0, j), e1 = mlp_input_element(s, t, 1, j), e = h ? e1 : e0;
+            const float other = h ? sh_or_one(e1, sh) : sh_or_one(e0, sh);
+            const float feature = row[e > 0 ? e : 0];
+            v[j] = e >= 0 ? feature : other;
+        }
+    }
+    return as_frag(make_uint4(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7])));
+}
+
+// a layer's result -> the next layer's operand: ReLU, then registers 8 s .. 8 s + 7 of row block b become k-step 2 b + s
+template <int MB>
+__device__ __forceinline__ void pack_hidden(const f32x16 (&acc)[MB], bf16x8 (&hb)[2 * MB]) {
+#pragma unroll
+    for (int b = 0; b < MB; ++b)
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            uint32_t w[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) w[q] = pack_bf16(fmaxf(acc[b][8 * sub + 2 * q], 0.f), fmaxf(acc[b][8 * sub + 2 * q + 1], 0.f));
+            hb[2 * b + sub] = as_frag(make_uint4(w[0], w[1], w[2], w[3]));
+        }
+}
+
+__device__ __forceinline__ f32x16 zero16() {
+    f32x16 z;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) z[i] = 0.f;
+    return z;
+}
+
+template <int WIDTH>
+__global__ __launch_bounds__(kBlock) void mlp_forward_kernel(Shape s, int n_out, int activation, const float* __restrict__ params,
+                                                             const float* __restrict__ input, uint32_t P, float* __restrict__ out) {
+    constexpr int MB = WIDTH / kTile, KW = WIDTH / kStep;
+    extern __shared__ __attribute__((aligned(16))) unsigned char image[];
+
+    // ---- the weight image, from the live fp32 parameters -----------------------------------------------------------------------------
+    const uint32_t chunks = num_frags(s) * 64u;
+    for (uint32_t c = threadIdx.x; c < chunks; c += kBlock) {
+        uint32_t src = 0;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (image_chunk_source(s, n_out, c, &src)) {
+            const float4 a = *reinterpret_cast<const float4*>(params + src), b = *reinterpret_cast<const float4*>(params + src + 8);
+            v = make_uint4(pack_bf16(a.x, a.y), pack_bf16(a.z, a.w), pack_bf16(b.x, b.y), pack_bf16(b.z, b.w));
+        }
+        *reinterpret_cast<uint4*>(image + (size_t)c * 16u) = v;
+    }
+    __syncthreads();
+
+    const int lane = threadIdx.x & (GRUT_WAVE - 1), r = lane & 31, h = lane >> 5;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / GRUT_WAVE));
+    const int nk0 = ksteps_first(s), nh = s.n_hidden_layers, cols = s.n_features + 3;
+    const uint32_t steps = (uint32_t)(((uint64_t)P + kColTiles * kTile - 1) / (kColTiles * kTile));
+
+    for (uint32_t step = blockIdx.x * kWavesPerBlock + wave; step < steps; step += gridDim.x * kWavesPerBlock) {
+        f32x16 acc[kColTiles][MB];
+        uint64_t pixel[kColTiles];
+        // ---- layer 0: the encoded input, k-step by k-step ---------------------------------------------------------------------------
+        const float* row[kColTiles];
+        f32x16 sh[kColTiles];
+#pragma unroll
+        for (int c = 0; c < kColTiles; ++c) {
+            pixel[c] = ((uint64_t)step * kColTiles + c) * kTile + r;
+            row[c] = input + (pixel[c] < P ? pixel[c] : (uint64_t)P - 1) * cols;   // a tail lane reads the last pixel and stores nothing
+            const float* u = row[c] + s.n_features;
+            sh[c] = sh_values(2.f * u[0] - 1.f, 2.f * u[1] - 1.f, 2.f * u[2] - 1.f);
+#pragma unroll
+            for (int m = 0; m < MB; ++m) acc[c][m] = zero16();
+        }
+        const unsigned char* w = image + image_offset(s, 0, 0, 0, lane);
+#pragma nounroll
+        for (int t = 0; t < nk0; ++t) {
+            bf16x8 b[kColTiles];
+#pragma unroll
+            for (int c = 0; c < kColTiles; ++c) b[c] = encode_step(s, t, h, row[c], sh[c]);
+#pragma unroll
+            for (int m = 0; m < MB; ++m) {
+                const bf16x8 a = as_frag(*reinterpret_cast<const uint4*>(w + (size_t)frag_in_layer(nk0, m, t) * kFragBytes));
+#pragma unroll
+                for (int c = 0; c < kColTiles; ++c) acc[c][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[c], acc[c][m], 0, 0, 0);
+            }
+        }
+        // ---- hidden layers 1 .. nh - 1 ---------------------------------------------------------------------------------------------
+        bf16x8 hb[kColTiles][KW];
+        for (int layer = 1; layer < nh; ++layer) {
+            w = image + image_offset(s, layer, 0, 0, lane);
+#pragma unroll
+            for (int c = 0; c < kColTiles; ++c) {
+                pack_hidden<MB>(acc[c], hb[c]);
+#pragma unroll
+                for (int m = 0; m < MB; ++m) acc[c][m] = zero16();
+            }
+#pragma unroll
+            for (int m = 0; m < MB; ++m)
+#pragma unroll
+                for (int t = 0; t < KW; ++t) {
+                    const bf16x8 a = as_frag(*reinterpret_cast<const uint4*>(w + (size_t)frag_in_layer(KW, m, t) * kFragBytes));
+#pragma unroll
+                    for (int c = 0; c < kColTiles; ++c) acc[c][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, hb[c][t], acc[c][m], 0, 0, 0);
+                }
+        }
+        // ---- the output layer: one row block, rows beyond n_out are zero in the image -----------------------------------------------
+        w = image + image_offset(s, nh, 0, 0, lane);
+        f32x16 o[kColTiles];
+#pragma unroll
+        for (int c = 0; c < kColTiles; ++c) {
+            pack_hidden<MB>(acc[c], hb[c]);
+            o[c] = zero16();
+        }
+#pragma unroll
+        for (int t = 0; t < KW; ++t) {
+            const bf16x8 a = as_frag(*reinterpret_cast<const uint4*>(w + (size_t)frag_in_layer(KW, 0, t) * kFragBytes));
+#pragma unroll
+            for (int c = 0; c < kColTiles; ++c) o[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, hb[c][t], o[c], 0, 0, 0);
+        }
+#pragma unroll
+        for (int c = 0; c < kColTiles; ++c) {
+            float* dst = out + pixel[c] * (uint64_t)n_out;
+#pragma unroll
+            for (int reg = 0; reg < 8; ++reg) {   // registers 0 .. 7 hold rows 0 .. 15
+                const int orow = mlp_out_row(reg, h);
+                float y = o[c][reg];
+                if (activation == GRUT_MLP_ACT_RELU) y = fmaxf(y, 0.f);
+                if (activation == GRUT_MLP_ACT_SIGMOID) y = 1.f / (1.f + __expf(-y));
+                if (pixel[c] < P && orow < n_out) dst[orow] = y;
+            }
+        }
+    }
+}
+
+bool shape_of(const GrutMlpConfig* c, Shape* s) {
+    if (!c) return false;
+    *s = Shape{c->n_features, c->sh_degree, c->n_hidden_layers, c->width};
+    return shape_ok(*s) && c->n_output_dims >= 1 && c->n_output_dims <= kOutRows && c->output_activation >= GRUT_MLP_ACT_NONE &&
+           c->output_activation <= GRUT_MLP_ACT_SIGMOID;
+}
+
+template <int WIDTH>
+int launch(hipStream_t stream, const Shape& s, const GrutMlpConfig* c, const float* params, const float* input, uint32_t P, float* out) {
+    int dev = 0, cus = 0;
+    GRUT_HIP(hipGetDevice(&dev));
+    GRUT_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const uint32_t bytes = lds_bytes(s);
+    const uint32_t steps = (uint32_t)(((uint64_t)P + kColTiles * kTile - 1) / (kColTiles * kTile));
+    const uint32_t need = (steps + kWavesPerBlock - 1) / kWavesPerBlock;
+    const uint32_t grid = need < (uint32_t)(cus > 0 ? cus : 1) ? need : (uint32_t)(cus > 0 ? cus : 1);
+    if (bytes > 64u * 1024u)
+        GRUT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_forward_kernel<WIDTH>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)bytes));
+    mlp_forward_kernel<WIDTH><<<grid, kBlock, bytes, stream>>>(s, c->n_output_dims, c->output_activation, params, input, P, out);
+    GRUT_HIP(hipGetLastError());
+    return GRUT_OK;
+}
+
+}  // namespace
+}  // namespace grut
+
+using namespace grut;
+
+extern "C" uint32_t grut_mlp_num_params(const GrutMlpConfig* config) {
+    Shape s;
+    return shape_of(config, &s) ? num_params(s) : 0u;
+}
+
+extern "C" uint32_t grut_mlp_lds_bytes(const GrutMlpConfig* config) {
+    Shape s;
+    return shape_of(config, &s) ? lds_bytes(s) : 0u;
+}
+
+extern "C" int grut_mlp_forward(void* stream, const GrutMlpConfig* config, const float* params, const float* input, uint32_t P, float* out) {
+    Shape s;
+    GRUT_REQUIRE(shape_of(config, &s), "grut_mlp_forward: width must be 64 or 128, sh_degree 1..4, n_hidden_layers >= 1, the padded encoded "
+                                       "width at most 128, n_output_dims 1..16 and the activation one of GRUT_MLP_ACT_*");
+    GRUT_REQUIRE(lds_bytes(s) != 0, "grut_mlp_forward: the weight image of this configuration does not fit into LDS (grut_mlp_lds_bytes)");
+    GRUT_REQUIRE(P > 0 && params && input && out, "grut_mlp_forward: num_pixels > 0, params, input and out are required");
+    GRUT_REQUIRE(((uintptr_t)params & 15u) == 0, "grut_mlp_forward: params must be 16-byte aligned");
+    const hipStream_t st = (hipStream_t)stream;
+    return s.width == 64 ? launch<64>(st, s, config, params, input, P, out) : launch<128>(st, s, config, params, input, P, out);
+}

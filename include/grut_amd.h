@@ -680,6 +680,44 @@ int grut_ppisp_backward(void* stream, uint32_t num_pixels, const float* rgb, con
                         const float* exposure, const float* color, const float* vignetting, const float* crf, const float* grad_out,
                         float* grad_rgb, float* grad_exposure, float* grad_color, float* grad_vignetting, float* grad_crf, float* partials);
 
+/* ---- NHT decoder network (threedgrut/model/feature_decoder.py: tinycudann's NetworkWithInputEncoding) -------------------------- */
+/* The network that turns a pixel's rendered features and ray direction into colour (model.feature_type: nht), forward only, as one
+ * fused pass: encoding, every layer and the output activation, the activations never leaving registers.  The model, which is THIS
+ * project's statement of what the reference's call surface leaves open:
+ *   input   [P, F + 3] contiguous fp32 DEVICE rows: F feature columns, then u = (dir * sh_scale + 1) / 2
+ *   encoding  columns 0 .. F-1 pass through; d = 2 u - 1 = (x, y, z), NOT normalised; the first L^2 (L = sh_degree, 1..4) of the real
+ *           SH polynomials, written for general d:
+ *             0.28209479177387814              -0.48860251190291987 y            0.48860251190291987 z          -0.48860251190291987 x
+ *             1.0925484305920792 xy            -1.0925484305920792 yz            0.94617469575755997 z^2 - 0.31539156525251999
+ *             -1.0925484305920792 xz           0.54627421529603959 (x^2 - y^2)   0.59004358992664352 y(-3x^2 + y^2)
+ *             2.8906114426405538 xyz           0.45704579946446572 y(1 - 5z^2)   0.3731763325901154 z(5z^2 - 3)
+ *             0.45704579946446572 x(1 - 5z^2)  1.4453057213202769 z(x^2 - y^2)   0.59004358992664352 x(-x^2 + 3y^2)
+ *           the width F + L^2 is padded with ONES to the next multiple of 16, K0 (a learnable first-layer bias when there is padding)
+ *   network n_hidden_layers layers of `width` neurons with ReLU, then an output layer; no biases; output activation GRUT_MLP_ACT_*
+ *   params  one flat fp32 array, the matrices in layer order, each row-major [out][in]: width x K0, (n_hidden_layers - 1) times
+ *           width x width, then 16 x width of which rows >= n_output_dims are never read
+ *   precision  the weights, the encoded input and every hidden activation after its ReLU are rounded to bf16 (nearest even); every sum
+ *           is fp32; the output layer's sum goes through its activation in fp32
+ *   out     [P, n_output_dims] contiguous fp32
+ * grut_mlp_forward takes width 64 or 128, K0 <= 128, 1 <= n_output_dims <= 16 and a configuration whose weight image fits into one
+ * workgroup's LDS: grut_mlp_lds_bytes returns the image's size in bytes, or 0 when it does not fit or the configuration is not taken;
+ * anything else is GRUT_ERR_BAD_INPUT before anything is launched.  Every workgroup builds the image from `params` (16-byte aligned) at
+ * launch: there is no prepared copy of the weights, a change of `params` by any means is seen by the next call.  No atomics: two calls
+ * on the same input are bitwise equal.  No allocation, no synchronisation, one launch on `stream`.
+ * grut_mlp_num_params: the length of `params` (0 for a configuration that is not taken). */
+enum { GRUT_MLP_ACT_NONE = 0, GRUT_MLP_ACT_RELU = 1, GRUT_MLP_ACT_SIGMOID = 2 };
+typedef struct GrutMlpConfig {
+    int32_t n_features;          /* F */
+    int32_t sh_degree;           /* L: L^2 SH values */
+    int32_t n_hidden_layers;
+    int32_t width;
+    int32_t n_output_dims;
+    int32_t output_activation;   /* GRUT_MLP_ACT_* */
+} GrutMlpConfig;
+uint32_t grut_mlp_num_params(const GrutMlpConfig* config);
+uint32_t grut_mlp_lds_bytes(const GrutMlpConfig* config);
+int grut_mlp_forward(void* stream, const GrutMlpConfig* config, const float* params, const float* input, uint32_t num_pixels, float* out);
+
 /* ---- nearest-neighbour initialisation (threedgrut/model/geometry.py) ----------------------------------------------- */
 /* Exact k nearest neighbours in 3-D, the device side of what the reference's initialisation takes from sklearn.neighbors:
  * k_nearest_neighbors (geometry.py:42-49, called at model.py:732 for the Gaussians' initial size), nearest_neighbors (geometry.py:52-73)

@@ -14,5 +14,7 @@ _il.import_module("3dgrut_amd.mcmc").install()
 _il.import_module("3dgrut_amd.losses").install()
 # the post-processing package (threedgrut/trainer.py:470 `from ppisp import PPISP, PPISPConfig`): the HIP PPISP unless one is installed
 _il.import_module("3dgrut_amd.ppisp").install()
+# the NHT decoder's network (threedgrut/model/feature_decoder.py:16 `import tinycudann as tcnn`): the HIP MLP unless one is installed
+_il.import_module("3dgrut_amd.tcnn").install()
 
 __all__ = ["Tracer"]
