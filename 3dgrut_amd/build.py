@@ -1,6 +1,7 @@
 """In-tree build of libgrut_amd.so with hipcc for gfx950 (cross-compiles without a GPU).
 
     python 3dgrut_amd/build.py [--force] [--verbose]
+    python 3dgrut_amd/build.py --variant NAME FILE.hip [flags...]
 
 One object per .hip file, rebuilt only when its sources are newer; linked into csrc/libgrut_amd.so,
 which travels to the GPU box with the repository snapshot.
@@ -15,7 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(CSRC, "libgrut_amd.so")
-SOURCES = ["scan_sort.hip", "gut_kernels.hip", "gut_poses.hip", "gut_render.hip", "gut_api.hip", "grt_kernels.hip", "grt_api.hip", "optim.hip", "mcmc.hip", "loss.hip", "densify.hip", "knn.hip", "ppisp.hip", "mlp.hip"]
+SOURCES = ["scan_sort.hip", "gut_kernels.hip", "gut_poses.hip", "gut_render.hip", "gut_render_k.hip", "gut_api.hip", "grt_kernels.hip", "grt_api.hip", "optim.hip", "mcmc.hip", "loss.hip", "densify.hip", "knn.hip", "ppisp.hip", "mlp.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-ffp-contract=fast",
          # SLP-packing scalar f32 math into v_pk_*_f32 costs register-pair shuffles (v_mov) and VGPRs on gfx950
@@ -30,19 +31,12 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-at
 # instructions in another order: gradient sweep 0.807 -> 0.792 ms, forward 0.449 -> 0.443 ms, step -1.1 % (A/B on one box, interleaved:
 # scripts/ab_sched_variants.sh, profiles/r06_sched_strategy_ab.txt).  Measured and NOT applied: gut_kernels.hip (the gradient gather loses
 # 12 us), grt_kernels.hip (trace forward -0.1 ms, replay backward +0.03: one file), max-memory-clause (slower everywhere).
-# The sorted hit buffer's kernels (SH radiance) LOSE with it (K = 16 frame 10.87 -> 11.32 ms), so gut_render.hip is compiled twice: part 0
-# (everything else, max-ILP) and part 1 (launch_render_k_fwd / _bwd and the kernels they instantiate, default strategy) - see the file's head.
+# The sorted hit buffer's kernels with SH radiance LOSE with it (K = 16 frame 10.87 -> 11.32 ms, 4 %) where the unsorted sweeps gain 1-2 % and
+# the feature sweeps 2.5 %: that is why they are a source of their own, gut_render_k.hip, built with the default strategy; what the two share
+# is gut_render_common.inl.
 # knn.hip reports distances recomputed in double that must round like the host's float64 arithmetic (no fused multiply-add there).
-FILE_FLAGS = {"grt_kernels.hip": ["-ffp-contract=on"], "gut_poses.hip": ["-ffp-contract=off"], "knn.hip": ["-ffp-contract=off"]}
-# translation units: (source, object, flags of this unit)
-UNITS = [(s_, s_.replace(".hip", ".o"), []) for s_ in SOURCES if s_ != "gut_render.hip"] + [
-    ("gut_render.hip", "gut_render.o", ["-DGRUT_RENDER_PART=0", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
-    ("gut_render.hip", "gut_render_k.o", ["-DGRUT_RENDER_PART=1"])]
-
-
-def unit_flags(src: str):
-    """Per-file + per-unit flags of `src`'s FIRST translation unit (what scripts/kernel_resources.py and valu_model.py compile with)."""
-    return [*FILE_FLAGS.get(src, []), *next((f for s_, _, f in UNITS if s_ == src), [])]
+FILE_FLAGS = {"grt_kernels.hip": ["-ffp-contract=on"], "gut_poses.hip": ["-ffp-contract=off"], "knn.hip": ["-ffp-contract=off"],
+              "gut_render.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 
 
 def _hipcc() -> str:
@@ -53,8 +47,9 @@ def _hipcc() -> str:
 
 
 def _deps():
+    """What every object depends on besides its own source: the headers, and this file (the flags)."""
     return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h", ".inl"))] + \
-           [os.path.join(HERE, "..", "include", "grut_amd.h")]
+           [os.path.join(HERE, "..", "include", "grut_amd.h"), os.path.abspath(__file__)]
 
 
 def _stale(target, sources):
@@ -64,34 +59,58 @@ def _stale(target, sources):
     return any(os.path.getmtime(s) > t for s in sources)
 
 
+def _object(src: str) -> str:
+    return os.path.join(CSRC, src.replace(".hip", ".o"))
+
+
+def compile_command(src: str, extra=(), out=None):
+    """The full compile argv of one source of SOURCES: the build's, the resource scripts' and the variants'."""
+    return [_hipcc(), "-x", "hip", *FLAGS, *FILE_FLAGS.get(src, []), *extra, "-c", os.path.join(CSRC, src), "-o", out or _object(src)]
+
+
+def _run(cmd, verbose=False):
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
+    if verbose and r.stderr:
+        print(r.stderr)
+
+
+def _link(objs, out, verbose=False):
+    _run([_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", out], verbose)
+
+
 def build(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
-    hipcc = _hipcc()
     deps = _deps()
-    objs, jobs = [], []
-    for src, obj, unit_flags in UNITS:
-        sp = os.path.join(CSRC, src)
-        if not os.path.exists(sp):
-            continue
-        op = os.path.join(CSRC, obj)
-        objs.append(op)
-        if force or _stale(op, [sp] + deps):
-            jobs.append([hipcc, "-x", "hip", *FLAGS, *FILE_FLAGS.get(src, []), *unit_flags, *extra_flags, "-c", sp, "-o", op])
-
-    def run(cmd):
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
-        if verbose and r.stderr:
-            print(r.stderr)
-
+    objs = [_object(src) for src in SOURCES]
+    jobs = [compile_command(src, extra_flags) for src, obj in zip(SOURCES, objs) if force or _stale(obj, [os.path.join(CSRC, src)] + deps)]
     with ThreadPoolExecutor(max_workers=4) as ex:
-        list(ex.map(run, jobs))
+        list(ex.map(lambda cmd: _run(cmd, verbose), jobs))
     if force or jobs or _stale(OUT, objs):
-        run([hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", OUT])
+        _link(objs, OUT, verbose)
     return OUT
 
 
+def variant(name: str, src: str, extra_flags=(), verbose: bool = False) -> str:
+    """One source compiled with extra flags (a tuning switch: -DGRT_FWD_WAVES=3; a build-time diagnostic: -DGRT_ONLY_DEGREE_4) and linked with
+    the in-tree objects of every other source into variants/libgrut_amd_NAME.so, which GRUT_AMD_LIB selects at load time."""
+    if src not in SOURCES:
+        raise ValueError(f"{src} is not one of {SOURCES}")
+    build(verbose=verbose)
+    vdir = os.path.join(HERE, "..", "variants")
+    os.makedirs(vdir, exist_ok=True)
+    obj = os.path.join(vdir, f"{src[:-4]}_{name}.o")
+    _run(compile_command(src, extra_flags, out=obj), verbose)
+    out = os.path.abspath(os.path.join(vdir, f"libgrut_amd_{name}.so"))
+    _link([obj if s_ == src else _object(s_) for s_ in SOURCES], out, verbose)
+    return out
+
+
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose="--verbose" in sys.argv))
+    args = [a for a in sys.argv[1:] if a != "--verbose"]
+    if args[:1] == ["--variant"]:
+        print(variant(args[1], args[2], args[3:], verbose="--verbose" in sys.argv))
+    else:
+        print(build(force="--force" in args, verbose="--verbose" in sys.argv))

@@ -888,67 +888,6 @@ __device__ __forceinline__ void trace_round(const GrtBvh& bvh, const RayW& r, fl
     }
 }
 
-// One optixTrace per LANE (round 6): every ray walks the tree on its own - its own current node, its own stack (LDS, `depth` words per
-// lane at `lstack[k * 64 + lane]`), the nearer child first - for rays that do NOT share their path: the hybrid tracer's bounced segments
-// (mirror, glass and PBR bounces leave a packet's 64 rays with 64 origins and directions).  The packet walk above visits the UNION of the
-// 64 paths one node after the other (thousands of ~0.66 us steps for a wave with a single live ray as for 64 incoherent ones); here a
-// step serves 64 different nodes at once and a round takes as many steps as its longest single path (a few hundred).  Same candidate test,
-// same per-lane buffers ordered by (distance, particle): the result of a round does not depend on the order in which candidates arrive, so
-// it equals the packet walk's bit for bit.  Pruning: the packet walk's own per-lane conditions, against the lane's current bound.
-// Returns false if some lane's stack overflowed (the caller repeats the round with the packet walk; not observed on the bench scenes).
-template <int G>
-__device__ __forceinline__ bool trace_round_lanes(const GrtBvh& bvh, const RayW& r, float tmin, float tmax, bool active, int lane,
-                                                  uint32_t* __restrict__ lstack, int depth, HitBufferT<G>& buf) {
-    buf.clear();
-    if (!__any(active)) return true;
-    constexpr uint32_t kDone = 0xFFFFFFFEu;
-    uint32_t cur = active ? 0u : kDone;   // root
-    int sp = 0;
-    bool overflow = false;
-    const float4* nodes4 = reinterpret_cast<const float4*>(bvh.nodes);
-    while (__any(cur != kDone)) {
-        if (cur != kDone) {
-            const float4 q0 = nodes4[4 * (size_t)cur], q1 = nodes4[4 * (size_t)cur + 1], q2 = nodes4[4 * (size_t)cur + 2], q3 = nodes4[4 * (size_t)cur + 3];
-            const uint32_t c0 = __float_as_uint(q3.x), c1 = __float_as_uint(q3.y);
-            float tn0, tf0, tn1, tf1;
-            bool ok0, ok1;
-            boxes_hit(q0, q1, q2, r, tn0, tf0, tn1, tf1, ok0, ok1);
-            const float bound = fminf(tmax, buf.t[G - 1]);
-            bool h0 = (c0 != kGrtNoChild) && ok0 && (tf0 >= tmin) && (tn0 <= tmax) && (tn0 - q3.z <= bound);
-            bool h1 = (c1 != kGrtNoChild) && ok1 && (tf1 >= tmin) && (tn1 <= tmax) && (tn1 - q3.w <= bound);
-            const bool l0 = h0 && (c0 & kGrtLeafBit), l1 = h1 && (c1 & kGrtLeafBit);
-            if (l0 || l1) {   // at most one pass per leaf child; the two leaves of a node are tested one after the other (the nearer box first)
-                const bool first1 = l1 && (!l0 || tn1 < tn0);
-#pragma unroll 1
-                for (int k = 0; k < 2; ++k) {
-                    const bool take1 = (k == 0) ? first1 : !first1;
-                    const bool doit = take1 ? l1 : l0;
-                    if (doit) {
-                        const uint32_t id = (take1 ? c1 : c0) & ~kGrtLeafBit;
-                        const Cand cd = candidate(bvh.inst + 12 * (size_t)id, r, tmin, buf.t[G - 1], id, buf.id[G - 1]);
-                        const bool reach = cd.ok && (cd.t < tmax) && (cd.tnear <= tmax) && hit_less(cd.t, id, buf.t[G - 1], buf.id[G - 1]);
-                        if (reach && (cd.t > tmin) && (cd.tfar >= tmin)) buf.insert(cd.t, id);
-                    }
-                }
-                h0 = h0 && !l0; h1 = h1 && !l1;
-            }
-            if (h0 && h1) {   // both inner children: the nearer one now, the other parked
-                const bool near0 = tn0 <= tn1;
-                if (sp < depth) lstack[sp * 64 + lane] = near0 ? c1 : c0; else overflow = true;
-                sp += sp < depth ? 1 : 0;
-                cur = near0 ? c0 : c1;
-            } else if (h0 || h1) {
-                cur = h0 ? c0 : c1;
-            } else if (sp > 0) {
-                cur = lstack[--sp * 64 + lane];
-            } else {
-                cur = kDone;
-            }
-        }
-    }
-    return !__any(overflow);
-}
-
 // Tight bounds of the hit distance of one particle for the rays of ONE packet (cone axis `k`, half angle theta).  With x = o + t d - mu
 // the closest-approach point, y = W x and u = W dh (dh the unit direction): y is perpendicular to u (t minimises |W x|) and |y| <= sqrt 3
 // (the ray touches the proxy box), and t |d| = v.dh + x.dh with x.dh = y.(S e), e = R^T dh, u = S^-1 e, (S e).u = 1, hence
@@ -1113,9 +1052,6 @@ __device__ __forceinline__ ListEntry load_list_entry(const GrtLists& L, const Gr
 // second pass goes through the deferred entries with whatever bound the first pass left.  Entries refined during a round carry their
 // flag only from the round's end (`pending`, LDS): in the second pass an entry without the flag has been tested by the first.
 constexpr uint32_t kGrtPendingCap = 512;
-#ifndef GRT_LIST_ILP
-#define GRT_LIST_ILP 1   // entries tested per iteration of list_round's work loop (2: two independent candidate chains)
-#endif
 template <bool COUNT, int G, bool GHOST = false, bool REFINE = false>
 __device__ __forceinline__ void list_round(const GrtLists& L, const GrtCone& cone, float dmin, float dmax, uint32_t le, uint32_t& start, const RayW& r,
                                            float tmin, float tmax, bool active, int lane, float4* __restrict__ s_ent /* [64][3] */, HitBufferT<G>& buf,
@@ -1162,77 +1098,6 @@ __device__ __forceinline__ void list_round(const GrtLists& L, const GrtCone& con
             int tested = 0;
             const unsigned long long tt0 = (COUNT && live) ? wall_clock64() : 0ull;
             const bool timed_tests = COUNT && live;
-#if GRT_LIST_ILP == 2
-            // Two live entries per iteration: their candidate tests are independent instruction chains (the second one's early-out uses
-            // the bound BEFORE the first one's insertion - a superset; `reach` re-checks against the buffer as it then stands, so
-            // decisions, buffers and ghosts are those of the one-by-one loop).  A packet's wave is latency-bound when its SIMD is not
-            // full - the last 45 % of the launch's span - and the two chains fill each other's issue gaps.
-            while (live) {
-                const int j0 = __ffsll((long long)live) - 1;
-                live &= live - 1;
-                const bool two = live != 0ull;
-                const int j1 = two ? __ffsll((long long)live) - 1 : j0;
-                live &= live - 1;   // (0 & -1 = 0 when there was no second entry)
-                const uint32_t id0 = (uint32_t)__builtin_amdgcn_readlane((int)my_id, j0), id1 = (uint32_t)__builtin_amdgcn_readlane((int)my_id, j1);
-                if (COUNT && lane == 0) tc.wave_leaves += two ? 2u : 1u;
-                const bool ft0 = REFINE && pass == 0 && ((fresh >> j0) & 1ull) && n_pending < kGrtPendingCap;
-                const bool ft1 = two && REFINE && pass == 0 && ((fresh >> j1) & 1ull) && n_pending + (ft0 ? 1u : 0u) < kGrtPendingCap;
-                float lo0 = 3.0e38f, hi0 = -3.0e38f, lo1 = 3.0e38f, hi1 = -3.0e38f;
-                if (active) {
-                    const float t_lo = GHOST ? ghosts->tie_t : tmin;
-                    const Cand c0 = GHOST ? candidate_abe<true, true>(s_ent[j0 * 3], s_ent[j0 * 3 + 1], s_ent[j0 * 3 + 2], r, t_lo, buf.t[G - 1], id0, buf.id[G - 1], ft0, true)
-                                          : candidate_abe<true>(s_ent[j0 * 3], s_ent[j0 * 3 + 1], s_ent[j0 * 3 + 2], r, t_lo, buf.t[G - 1], id0, buf.id[G - 1], ft0, true);
-                    Cand c1 = GHOST ? candidate_abe<true, true>(s_ent[j1 * 3], s_ent[j1 * 3 + 1], s_ent[j1 * 3 + 2], r, t_lo, buf.t[G - 1], id1, buf.id[G - 1], ft1, true)
-                                    : candidate_abe<true>(s_ent[j1 * 3], s_ent[j1 * 3 + 1], s_ent[j1 * 3 + 2], r, t_lo, buf.t[G - 1], id1, buf.id[G - 1], ft1, true);
-                    if (!two) { c1.ok = false; c1.box = false; }
-                    auto take = [&](const Cand& cd, uint32_t id, float& tl, float& th) {
-                        if (REFINE && cd.box) { tl = cd.t; th = cd.t; }
-                        const bool reach = cd.ok && (cd.t < tmax) && (cd.tnear <= tmax) && hit_less(cd.t, id, buf.t[G - 1], buf.id[G - 1]);
-                        const bool in_range = reach && (cd.t > tmin);
-                        const bool ins = in_range && (cd.tfar >= tmin);
-                        if (GHOST && ((in_range && !ins) || (reach && !in_range && hit_less(ghosts->tie_t, ghosts->tie_id, cd.t, id)))) ghosts->add(cd.tfar, id);
-                        if (COUNT) {
-                            tc.leaf_tests++; tc.rej[cd.ok ? 0 : cd.why]++;
-                            const unsigned long long ms = __ballot(cd.ok || cd.why != 1), mi = __ballot(ins);
-                            if (ms && lane == __ffsll((long long)ms) - 1) tc.wave_slab++;
-                            if (mi && lane == __ffsll((long long)mi) - 1) tc.wave_insert++;
-                        }
-                        if (ins) {
-                            buf.insert(cd.t, id);
-                            if (COUNT) tc.inserts++;
-                        }
-                    };
-                    take(c0, id0, lo0, hi0);
-                    if (two) take(c1, id1, lo1, hi1);
-                }
-                if (ft0 || ft1) {
-                    float l0, h0, l1, h1;
-                    wave_min_max(lo0, hi0, l0, h0);
-                    wave_min_max(lo1, hi1, l1, h1);
-                    if (ft0) {
-                        if (lane == 0) {
-                            __hip_atomic_store(reinterpret_cast<unsigned long long*>(L.bounds + base + (uint32_t)j0),
-                                               (unsigned long long)__float_as_uint(l0) | ((unsigned long long)__float_as_uint(h0) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            pending[n_pending] = base + (uint32_t)j0;
-                        }
-                        ++n_pending;
-                    }
-                    if (ft1) {
-                        if (lane == 0) {
-                            __hip_atomic_store(reinterpret_cast<unsigned long long*>(L.bounds + base + (uint32_t)j1),
-                                               (unsigned long long)__float_as_uint(l1) | ((unsigned long long)__float_as_uint(h1) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            pending[n_pending] = base + (uint32_t)j1;
-                        }
-                        ++n_pending;
-                    }
-                }
-                tested += 2;
-                if ((tested & 7) == 0 && live) {
-                    wmax_bound = wave_max_nonneg(active ? fminf(tmax, buf.t[G - 1]) : -1.f);
-                    live &= __ballot(!(my_lo > wmax_bound));
-                }
-            }
-#else
             while (live) {
                 const int j = __ffsll((long long)live) - 1;
                 live &= live - 1;
@@ -1276,7 +1141,6 @@ __device__ __forceinline__ void list_round(const GrtLists& L, const GrtCone& con
                     live &= __ballot(!(my_lo > wmax_bound));
                 }
             }
-#endif
             if (timed_tests) tc.test_ticks += wall_clock64() - tt0;
             __syncthreads();
             if (beyond) break;
@@ -1508,17 +1372,6 @@ template <int DEG, bool COUNT, bool UNI, bool LOG, bool GEN>
 #ifndef GRT_FWD_WAVES
 #define GRT_FWD_WAVES 4
 #endif
-#ifndef GRT_HIT_PREFETCH
-#define GRT_HIT_PREFETCH 0
-#endif
-// GRT_FWD_PRIO = K > 0: a packet raises its wave's issue priority by one step every K trace rounds (s_setprio 1..3).  A packet's lifetime
-// is its number of wave-level tests (correlation 0.99) and nothing known before the launch predicts it (list length: 0.44), but the
-// lifetimes are heavy-tailed - a packet that has already run many rounds is one of the long ones - and the launch ends with its longest
-// packets (last third of the span at falling occupancy): letting those win the issue arbitration against the three lighter packets of
-// their SIMD while the chip is still full shortens the tail without touching the order of the launch (every reordering lost to locality).
-#ifndef GRT_FWD_PRIO
-#define GRT_FWD_PRIO 0
-#endif
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GRT_FWD_WAVES, GRT_FWD_WAVES))) void grt_trace_fwd_kernel(GrtTraceParams P, GrtBvh bvh, const float4* __restrict__ density12,
                                                            const float* __restrict__ sph, const float* __restrict__ ray_o,
                                                            const float* __restrict__ ray_d, float* __restrict__ out_rad,
@@ -1579,7 +1432,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GRT_FWD_WAVE
     bool ghost_overflow = false;   // LOG: a round of this ray saw more ghosts than a chunk holds
     float tmin_prev1 = -3.0e38f, tmin_prev2 = -3.0e38f;   // LOG: tmin of the previous round and of the one before (GhostLog::min_tfar)
     uint32_t last_id = 0xFFFFFFFFu;                       // LOG: the last processed hit is (tLast, last_id)
-    uint32_t rounds_done = 0u;                            // GRT_FWD_PRIO
 
     // one chunk of the hit log per (wave, trace round)
     auto open_chunk = [&]() -> uint32_t* {
@@ -1686,31 +1538,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GRT_FWD_WAVE
             sh_basis16(P.sph_degree, dir, basis);
         }
         // processHit (gaussianParticles.cuh:337-405) for the round's hits in order, while the ray is above min_transmittance
-#if GRT_HIT_PREFETCH
-        // the next hit's parameter row is requested while this hit is evaluated (a lone wave otherwise waits a memory round trip per hit, and
-        // another one for the SH row of an accepted hit: one word of each of its cache lines is touched ahead)
-        uint32_t id_next = s_hit_id[lane];
-        float4 na = make_float4(0.f, 0.f, 0.f, 0.f), nq = na, ns = na;
-        float touch = 0.f;
-        auto request = [&](uint32_t idn) {
-            if (running && idn != 0xFFFFFFFFu) {
-                const uint32_t pn = particle_of(P, idn);
-                na = density12[3 * (size_t)pn]; nq = density12[3 * (size_t)pn + 1]; ns = density12[3 * (size_t)pn + 2];
-                if (!P.nht && !P.sph_half) { const float* c = sph + (size_t)pn * 3 * P.ncoef; touch = c[0] + c[3 * P.ncoef - 1]; }
-            }
-        };
-        request(id_next);
-#endif
 #pragma unroll 1
         for (int i = 0; i < k_round; ++i) {
-#if GRT_HIT_PREFETCH
-            const uint32_t id = id_next;
-            const float4 ca_ = na, cq_ = nq, cs_ = ns;
-            asm volatile("" :: "v"(touch));
-            if (i + 1 < kGrtMaxHits) { id_next = s_hit_id[(i + 1) * 64 + lane]; request(id_next); }
-#else
             const uint32_t id = s_hit_id[i * 64 + lane];
-#endif
             const float hit_t = s_hit_t[i * 64 + lane];
             const bool process = running && (id != 0xFFFFFFFFu) && (T > P.min_transmittance);
             if (!__any(process)) break;  // ascending list: nothing further for any lane
@@ -1747,13 +1577,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GRT_FWD_WAVE
             }
             if (process) {
                 const uint32_t pid = particle_of(P, id);
-#if GRT_HIT_PREFETCH
-                Particle p;
-                p.pos = mk3(ca_.x, ca_.y, ca_.z); p.density = ca_.w; p.quat = cq_; p.scl = mk3(cs_.x, cs_.y, cs_.z);
-                p.rotT = quat_wxyz_to_rotT(cq_.x, cq_.y, cq_.z, cq_.w);
-#else
                 const Particle p = load_particle(density12, pid);
-#endif
                 const HitGeom g = hit_geometry<DEG>(P, p, r);
                 if (g.accept) {
                     const float weight = g.galpha * T;
@@ -1789,12 +1613,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GRT_FWD_WAVE
         }
         if (!full) running = false;   // the round held every remaining candidate of this ray
         if (COUNT) { const unsigned long long ph3 = wall_clock64(); tc.phase[0] += ph1 - ph0; tc.phase[1] += ph2 - ph1; tc.phase[2] += ph3 - ph2; }
-#if GRT_FWD_PRIO > 0
-        ++rounds_done;
-        if (rounds_done == 1u * GRT_FWD_PRIO) __builtin_amdgcn_s_setprio(1);
-        else if (rounds_done == 2u * GRT_FWD_PRIO) __builtin_amdgcn_s_setprio(2);
-        else if (rounds_done == 3u * GRT_FWD_PRIO) __builtin_amdgcn_s_setprio(3);
-#endif
     }
     if (!in_image) return;
     store_radiance(P, out_rad, pix, rad);
@@ -2853,11 +2671,6 @@ __device__ __forceinline__ MeshHit mesh_closest(const GrtMeshView& m, const RayW
 // REFINE (LISTS only): this call is the LAST scan of the packet's list by a set of rays that contains every ray of any later scan —
 // list_round may then keep exact per-entry intervals (see there).  The hybrid tracer scans the list twice in its first iteration
 // (the diffuse rays, then all rays): only the second scan refines.
-#ifndef GRT_LANE_WALK
-#define GRT_LANE_WALK 0   // 1: bounced segments walk the tree per lane (trace_round_lanes).  Built and measured in round 6: bit-identical, SLOWER - config 5
-                          // 98.7 vs 81 ms: the sparse scene's rays never fill their buffers, so a single ray's path through 2 M particles is thousands of
-                          // nodes long, and a per-lane step is four divergent 16-byte gathers at two waves per SIMD instead of one scalar fetch
-#endif
 template <int DEG, bool LISTS = false, bool REFINE = false>
 __device__ __forceinline__ void trace_segment(const GrtTraceParams& P, const GrtBvh& bvh, const float4* __restrict__ density12,
                                               const float* __restrict__ sph, const RayW& r, float tmin, float tmax, bool active, int lane,
@@ -2885,14 +2698,8 @@ __device__ __forceinline__ void trace_segment(const GrtTraceParams& P, const Grt
                                                                      reinterpret_cast<float4*>(s_hit_t), buf, tc, nullptr, s_hit_id + kGrtMaxGhosts * 64, &list_span,
                                                                      P.list_mark);
             else {
-                // rays with their own origins (bounced segments): one walk per lane, its stack in the LDS words of the round's hit arrays - which
-                // hold nothing while the round is gathered (32 levels per lane; deeper: the round is repeated by the packet walk)
-                static_assert(sizeof(float) == 4 && kGrtMaxHits * 64 * 2 >= 32 * 64, "the per-lane stacks live in s_hit_t + s_hit_id");
-                bool done = false;
-                if (GRT_LANE_WALK)   // (s_hit_id = s_hit_t + 16 x 64 words: the caller's ONE array, grt_hybrid_kernel)
-                    done = trace_round_lanes<kGrtMaxHits>(bvh, r, tLast + eps, t1 + eps, running, lane, reinterpret_cast<uint32_t*>(s_hit_t), 32, buf);
-                if (!done) trace_round<false, kGrtMaxHits>(bvh, r, tLast + eps, t1 + eps, running, lane, s_stack, buf, tc);
-                __syncthreads();   // single-wave workgroup: the stacks' last reads before the hit arrays are written
+                trace_round<false, kGrtMaxHits>(bvh, r, tLast + eps, t1 + eps, running, lane, s_stack, buf, tc);
+                __syncthreads();   // single-wave workgroup: the walk is over before the hit arrays are written
             }
             buf.store(s_hit_t, s_hit_id, lane);
         }
@@ -3141,13 +2948,8 @@ __device__ __forceinline__ f3 pg_background(const GrtMeshView& m, f3 d) {   // g
 // GEN = false: render.primitive_type instances with fp32 SH rows (the playground's default) - every `prim` comparison of the candidate test
 // and of the per-hit code folds away, as in the training forward's default instantiation
 template <int DEG, bool GEN = true>
-#ifndef GRT_HYBRID_WAVES
-#define GRT_HYBRID_WAVES 0   // 0: the allocator's own choice (219 registers, 2 waves per SIMD)
-#endif
+// (register allocation left to the compiler: 219 registers, 2 waves per SIMD)
 __global__ __launch_bounds__(64)
-#if GRT_HYBRID_WAVES > 0
-__attribute__((amdgpu_waves_per_eu(GRT_HYBRID_WAVES, GRT_HYBRID_WAVES)))
-#endif
 void grt_hybrid_kernel(GrtTraceParams P, GrtBvh bvh, GrtMeshView mesh, GrtHybridParams hp,
                                                         const float4* __restrict__ density12, const float* __restrict__ sph,
                                                         const float* __restrict__ ray_o, const float* __restrict__ ray_d,
@@ -3155,7 +2957,7 @@ void grt_hybrid_kernel(GrtTraceParams P, GrtBvh bvh, GrtMeshView mesh, GrtHybrid
                                                         float* __restrict__ out_alpha, float* __restrict__ out_last_ray,
                                                         uint32_t* __restrict__ out_bounces, GrtLists lists) {
     __shared__ uint32_t s_stack[kGrtStackDepth];
-    __shared__ float s_hits[2 * kGrtMaxHits * 64];   // one array: the per-lane walk's stacks span both halves (trace_segment)
+    __shared__ float s_hits[2 * kGrtMaxHits * 64];   // one array: the hit distances, then the hit ids
     float* s_hit_t = s_hits;
     uint32_t* s_hit_id = reinterpret_cast<uint32_t*>(s_hits + kGrtMaxHits * 64);
     if (!GEN) { P.prim = GRUT_PRIM_INSTANCES; P.sph_half = 0; }
@@ -3321,7 +3123,7 @@ void grt_launch_refit(hipStream_t s, uint32_t N, const float* aabb, const float*
     if (todo && N > 2) hipLaunchKernelGGL(grt_refit_finish_kernel, dim3(1), dim3(1024), 0, s, N, passes, aabb, slack, nodes, done, todo);
 }
 
-// (GRT_ONLY_DEGREE_4: development builds of kernel variants - scripts/build_variant.sh - instantiate the default kernel degree only: a
+// (GRT_ONLY_DEGREE_4: development builds of kernel variants - 3dgrut_amd/build.py: variant - instantiate the default kernel degree only: a
 // quarter of the file's four minutes of compile time)
 #ifdef GRT_ONLY_DEGREE_4
 #define GRT_DISPATCH_DEGREE(DEG, ...) { constexpr int D_ = 4; __VA_ARGS__; }

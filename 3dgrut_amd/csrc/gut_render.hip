@@ -21,444 +21,24 @@
 //     up with a quarter of the wave total of term l mod 16) and written to the tile entry's own SLOT (one per entry and
 //     half tile, no atomics: gradients are bitwise reproducible); quaternion, scale and position gradients are
 //     contracted from (B, M) once per particle by the gather kernel, not per pixel.
-#include <hip/hip_fp16.h>
+#include "gut_render_common.inl"
 
-#include "gut_internal.hpp"
-// This file is compiled TWICE (3dgrut_amd/build.py): GRUT_RENDER_PART=0 -> gut_render.o, everything except the launchers of the sorted hit
-// buffer with SH radiance, built with the backend's max-ILP scheduling strategy (the unsorted sweeps gain 1-2 %, the feature sweeps 2.5 %);
-// GRUT_RENDER_PART=1 -> gut_render_k.o, launch_render_k_fwd / launch_render_k_bwd and the kernels they instantiate, with the default strategy
-// (max-ILP costs the K = 16 frame 4 %: 10.87 -> 11.32 ms).  Undefined (a plain compile of the file): both parts, as before.
-#ifndef GRUT_RENDER_PART
-#define GRUT_RENDER_PART 2
-#endif
-
-// tuning switches of the gradient sweep (scripts/build_variant.sh -D...)
-#ifndef GRUT_BWD_FULL_REDUCE
-#define GRUT_BWD_FULL_REDUCE 2   // 0: row partials through LDS, 1: DPP butterfly + lane swaps, 2: transposition through LDS (r02j: 0.887 -> 0.85 ms)
-#endif
+// tuning switch of the gradient sweep (scripts/build_variant.sh NAME gut_render.hip -D...)
 #ifndef GRUT_BWD_WAVES
 #define GRUT_BWD_WAVES 4   // waves per SIMD the register allocator is held to (0: its own choice, 130 VGPRs = 3 waves); measured r02b:
 #endif                     // rows / 3 waves 0.917 ms, rows / 4 waves 0.910, lane-swap reduce / 3 waves 0.936, lane-swap reduce / 4 waves 0.891
+                           // ("rows" and "lane-swap reduce": the two retired forms of the per-entry reduction, GRUT_BWD_FULL_REDUCE 0 / 1 in
+                           // profiles/r06_experiments_not_kept.txt; the kept transposition through LDS took the 4-wave build from 0.887 to 0.85 ms)
 
 namespace grut {
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------
-// rays (rayPayload.cuh:75-108, bounding_box.h:89-140)
-// ---------------------------------------------------------------------------------------------
-struct Ray {
-    f3 o, d;
-    float tmin, tmax;
-    bool valid;
-    bool inside;   // pixel lies in the image (a ray that misses the scene box is inside but not valid)
-};
-__device__ __forceinline__ void swapf(float& a, float& b) { const float t = a; a = b; b = t; }
-// (a.x b.x + a.y b.y) + a.z b.z with every product and sum rounded on its own (the checker's v3_dot under -ffp-contract=off)
-__device__ __forceinline__ float rn_dot3(float ax, float ay, float az, f3 b) { return add_rn(add_rn(mul_rn(ax, b.x), mul_rn(ay, b.y)), mul_rn(az, b.z)); }
-__device__ __forceinline__ float rn_dot3(f3 a, f3 b) { return rn_dot3(a.x, a.y, a.z, b); }
-__device__ __forceinline__ Ray init_ray(const GutParams& P, const float* __restrict__ ray_o, const float* __restrict__ ray_d,
-                                        int px, int py) {
-    Ray r;
-    r.valid = false;
-    r.inside = false;
-    r.o = mk3(0.f, 0.f, 0.f);
-    r.d = mk3(0.f, 0.f, 1.f);
-    r.tmin = r.tmax = 0.f;
-    if (px >= P.W || py >= P.H) return r;
-    r.inside = true;
-    const size_t pix = (size_t)py * P.W + px;
-    const f3 so = mk3(ray_o[3 * pix], ray_o[3 * pix + 1], ray_o[3 * pix + 2]);
-    const f3 sd = mk3(ray_d[3 * pix], ray_d[3 * pix + 1], ray_d[3 * pix + 2]);
-    const FramePoses& FP = frame_poses(P);
-    const float* R = FP.s2w_R;
-    // world-space ray = pose . (o, d) (rayPayload.cuh:75-108) in the checker's operation order - rows dotted left to right, separately
-    // rounded, then the translation: the sorted mode orders hits by distances computed from these bits (oracle_order_hit_t)
-    r.o = mk3(add_rn(rn_dot3(R[0], R[1], R[2], so), FP.s2w_t[0]), add_rn(rn_dot3(R[3], R[4], R[5], so), FP.s2w_t[1]),
-              add_rn(rn_dot3(R[6], R[7], R[8], so), FP.s2w_t[2]));
-    r.d = mk3(rn_dot3(R[0], R[1], R[2], sd), rn_dot3(R[3], R[4], R[5], sd), rn_dot3(R[6], R[7], R[8], sd));
-    const float lo = -1e6f, hi = 1e6f, big = 3.4028234663852886e+38f;
-    float tmin = (lo - r.o.x) / r.d.x, tmax = (hi - r.o.x) / r.d.x;
-    if (tmin > tmax) swapf(tmin, tmax);
-    float tymin = (lo - r.o.y) / r.d.y, tymax = (hi - r.o.y) / r.d.y;
-    if (tymin > tymax) swapf(tymin, tymax);
-    bool miss = (tmin > tymax) || (tymin > tmax);
-    if (tymin > tmin) tmin = tymin;
-    if (tymax < tmax) tmax = tymax;
-    float tzmin = (lo - r.o.z) / r.d.z, tzmax = (hi - r.o.z) / r.d.z;
-    if (tzmin > tzmax) swapf(tzmin, tzmax);
-    miss = miss || (tmin > tzmax) || (tzmin > tmax);
-    if (tzmin > tmin) tmin = tzmin;
-    if (tzmax < tmax) tmax = tzmax;
-    if (miss) { tmin = big; tmax = big; }
-    r.tmin = fmaxf(tmin, 0.f);
-    r.tmax = tmax;
-    r.valid = r.tmax > r.tmin;
-    return r;
-}
-
-// The pixel pair of a lane and the wave-level facts about its rays.
-struct RayPair {
-    p3 o, d;
-    v2f tmin, tmax;
-    bool valid0, valid1;
-    bool inside0, inside1;
-    int px, py0, py1;
-    bool uniform_origin;  // every valid ray of the wave starts at `origin`
-    f3 origin;
-};
-__device__ __forceinline__ RayPair init_ray_pair(const GutParams& P, const float* __restrict__ ray_o, const float* __restrict__ ray_d,
-                                                 uint32_t tile, uint32_t half, int lane) {
-    RayPair rp;
-    rp.px = (int)(tile % P.gx) * 16 + (lane & 15);
-    rp.py0 = (int)(tile / P.gx) * 16 + (int)half * 8 + (lane >> 4);
-    rp.py1 = rp.py0 + 4;
-    const Ray a = init_ray(P, ray_o, ray_d, rp.px, rp.py0), b = init_ray(P, ray_o, ray_d, rp.px, rp.py1);
-    rp.o = p3{v2f{a.o.x, b.o.x}, v2f{a.o.y, b.o.y}, v2f{a.o.z, b.o.z}};
-    rp.d = p3{v2f{a.d.x, b.d.x}, v2f{a.d.y, b.d.y}, v2f{a.d.z, b.d.z}};
-    rp.tmin = v2f{a.tmin, b.tmin};
-    rp.tmax = v2f{a.tmax, b.tmax};
-    rp.valid0 = a.valid;
-    rp.valid1 = b.valid;
-    rp.inside0 = a.inside;
-    rp.inside1 = b.inside;
-    // wave-uniform origin?  take the first valid ray as the candidate
-    const unsigned long long m0 = __ballot(a.valid), m1 = __ballot(b.valid);
-    f3 cand = mk3(0.f, 0.f, 0.f);
-    if (m0) {
-        const int src = __ffsll((long long)m0) - 1;
-        cand = mk3(__shfl(a.o.x, src, 64), __shfl(a.o.y, src, 64), __shfl(a.o.z, src, 64));
-    } else if (m1) {
-        const int src = __ffsll((long long)m1) - 1;
-        cand = mk3(__shfl(b.o.x, src, 64), __shfl(b.o.y, src, 64), __shfl(b.o.z, src, 64));
-    }
-    const bool same0 = !a.valid || (a.o.x == cand.x && a.o.y == cand.y && a.o.z == cand.z);
-    const bool same1 = !b.valid || (b.o.x == cand.x && b.o.y == cand.y && b.o.z == cand.z);
-    rp.uniform_origin = __all(same0 && same1);
-    rp.origin = cand;
-    return rp;
-}
-
-// block -> (virtual tile, half) with both halves of a tile on one XCD (block b runs on XCD b % 8)
-// i -> (i * k') mod n with k' the first number >= k coprime to n: a bijection of [0, n) that sends neighbours far apart.  Launch
-// order = memory order keeps the waves in flight on one band of the image, all heavy or all light at a time; a strided order mixes them.
-__device__ __forceinline__ uint32_t stride_permute(uint32_t i, uint32_t n, uint32_t k) {
-    if (n < 3u) return i;
-    k %= n;
-    if (k < 2u) k = 2u;
-    while (true) {
-        uint32_t a = k, b = n;
-        while (b) { const uint32_t t = a % b; a = b; b = t; }
-        if (a == 1u) break;
-        ++k;
-    }
-    return (uint32_t)(((unsigned long long)i * k) % n);
-}
-__device__ __forceinline__ void half_mapping(uint32_t b, uint32_t& vtile, uint32_t& half) {
-    const uint32_t xcd = b & 7u, slot = b >> 3;
-    vtile = ((slot >> 1) << 3) + xcd;
-    half = slot & 1u;
-}
-
-// ---------------------------------------------------------------------------------------------
-// staged tile entry: 6 x float4 in LDS
-//   r0 = M.r0, pos.x | r1 = M.r1, pos.y | r2 = M.r2, pos.z      M = diag(1/scale) R^T  (gaussianParticles.slang:96-110)
-//   r3 = scale.xyz (fwd) or 1/scale.xyz (bwd), density
-//   r4 = clamped radiance rgb, g_max
-//   r5 = u0 = M (origin - pos) (uniform-origin waves), as_float(expansion position of the entry)
-// Padding entries (index 0xFFFFFFFF) get M = I and g_max = 0: finite everywhere, never accepted.
-// ---------------------------------------------------------------------------------------------
-constexpr int kRecQuads = 6;
-
-struct RawEntry {
-    uint32_t idx, pos;   // particle, expansion position of the entry (its gradient slot)
-    float4 a, q, s;
-    f3 rgb;
-};
-// the sorted lists carry expansion positions; pos_particle maps them to particles (0xFFFFFFFF = padding)
-// direct lists (rec64 != null, GutParams::rec64): the sorted payloads ARE the particles, one 64-byte record each; the gradient slot
-// of an entry is the particle's part_offset (in the record) + the ordinal in the upper key bits
-struct EntryLists {
-    const uint32_t* __restrict__ sorted_pos;
-    const uint32_t* __restrict__ pos_particle;
-    const float4* __restrict__ rec64;
-    const uint32_t* __restrict__ sorted_keys;
-    uint32_t ord_shift;
-};
-__host__ __device__ inline EntryLists entry_lists(const GutParams& P, const uint32_t* sorted_pos, const uint32_t* pos_particle) {
-    return EntryLists{sorted_pos, P.rec64 ? nullptr : pos_particle, P.rec64, P.sorted_keys, P.ord_shift};
-}
-template <bool WITH_POS = true>
-__device__ __forceinline__ RawEntry load_entry(uint32_t e, uint32_t end, const EntryLists& lists,
-                                               const float4* __restrict__ density12, const float* __restrict__ rgb) {
-    RawEntry r;
-    r.idx = 0xFFFFFFFFu;
-    r.pos = 0u;
-    r.a = r.q = r.s = make_float4(0.f, 0.f, 0.f, 0.f);
-    r.rgb = mk3(0.f, 0.f, 0.f);
-    if (e < end && lists.rec64) {
-        r.idx = lists.sorted_pos[e];
-        if (r.idx != 0xFFFFFFFFu) {
-            const float4* rec = lists.rec64 + 4 * (size_t)r.idx;
-            r.a = rec[0]; r.q = rec[1]; r.s = rec[2];
-            const float4 c = rec[3];
-            r.rgb = mk3(c.x, c.y, c.z);
-            if (WITH_POS) r.pos = __float_as_uint(r.s.w) + (lists.sorted_keys[e] >> lists.ord_shift);
-        }
-    } else if (e < end) {
-        r.pos = lists.sorted_pos[e];
-        r.idx = lists.pos_particle[r.pos];
-        if (r.idx != 0xFFFFFFFFu) {
-            r.a = density12[3 * (size_t)r.idx + 0];
-            r.q = density12[3 * (size_t)r.idx + 1];
-            r.s = density12[3 * (size_t)r.idx + 2];
-            if (rgb) r.rgb = mk3(rgb[3 * (size_t)r.idx], rgb[3 * (size_t)r.idx + 1], rgb[3 * (size_t)r.idx + 2]);
-        }
-    }
-    return r;
-}
-template <int DEG, bool INVERSE_SCALE>
-__device__ __forceinline__ void stage_entry(const GutParams& P, const RawEntry& r, bool uniform_origin, f3 origin, float4* __restrict__ rec) {
-    float4 r0 = make_float4(1.f, 0.f, 0.f, 0.f), r1 = make_float4(0.f, 1.f, 0.f, 0.f), r2 = make_float4(0.f, 0.f, 1.f, 0.f);
-    float4 r3 = make_float4(1.f, 1.f, 1.f, 0.f), r4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 r5 = make_float4(0.f, 0.f, 0.f, __uint_as_float(0xFFFFFFFFu));
-    if (r.idx != 0xFFFFFFFFu) {
-        const m3 rt = quat_wxyz_to_rotT(r.q.x, r.q.y, r.q.z, r.q.w);
-        const float ix = __builtin_amdgcn_rcpf(r.s.x), iy = __builtin_amdgcn_rcpf(r.s.y), iz = __builtin_amdgcn_rcpf(r.s.z);
-        r0 = make_float4(rt.r0.x * ix, rt.r0.y * ix, rt.r0.z * ix, r.a.x);
-        r1 = make_float4(rt.r1.x * iy, rt.r1.y * iy, rt.r1.z * iy, r.a.y);
-        r2 = make_float4(rt.r2.x * iz, rt.r2.y * iz, rt.r2.z * iz, r.a.z);
-        r3 = INVERSE_SCALE ? make_float4(ix, iy, iz, r.a.w) : make_float4(r.s.x, r.s.y, r.s.z, r.a.w);
-        const float need = fmaxf(P.min_response, P.min_alpha / r.a.w);   // response must exceed this
-        const float gmax = (P.max_alpha > P.min_alpha && r.a.w > 0.f) ? response_gray_limit<DEG>(need) : 0.f;
-        r4 = make_float4(fmaxf(r.rgb.x, 0.f), fmaxf(r.rgb.y, 0.f), fmaxf(r.rgb.z, 0.f), gmax);
-        if (uniform_origin) {
-            const f3 dl = origin - mk3(r.a.x, r.a.y, r.a.z);
-            r5.x = dot(mk3(r0.x, r0.y, r0.z), dl);
-            r5.y = dot(mk3(r1.x, r1.y, r1.z), dl);
-            r5.z = dot(mk3(r2.x, r2.y, r2.z), dl);
-        }
-        r5.w = __uint_as_float(r.pos);
-    }
-    rec[0] = r0; rec[1] = r1; rec[2] = r2; rec[3] = r3; rec[4] = r4; rec[5] = r5;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Half-tile culling of staged entries (round 4).  A tile's list is binned for the 16x16 tile by the reference's 2-D test; the wave owns
-// 16x8 of it, and 36 % of the entries a wave evaluates on the bench frame are accepted by none of its 128 pixels - each
-// of them costs the pair geometry.  The accept test is a LINE - sphere test in the particle's canonical frame (|v x u|^2 < gmax |v|^2:
-// the line through u along v passes the origin closer than r = sqrt(gmax)), so an entry whose sphere misses every line of the wave can
-// be dropped when it is staged, and no result changes.  The lines of a wave are bounded, for ANY camera model, by the pyramid of its
-// own rays: in a frame (a, e1, e2) around the first valid ray every ray is a + x e1 + y e2 up to scale, and the wave reduces
-// [x0, x1] x [y0, y1] once.  M maps the pyramid's four faces to planes through u spanned by (M c, M e2) / (M c, M e1) with c a corner
-// direction; det[M c, M e1, M e2] = det M > 0 fixes which side is out.  The lines also extend BEHIND the apex; that mirror pyramid lies
-// behind the plane through u with normal M e1 x M e2 (the image of the camera plane normal to a), so the entry is dropped only if its
-// sphere is wholly in front of that plane and wholly outside one face.  All comparisons carry r' = 1.001 r + 1e-5 |u| (the accept test
-// and these triple products both cancel to ~1e-7 |u|).
-// ---------------------------------------------------------------------------------------------
-struct WavePyramid {
-    bool on;          // wave-uniform: the bound exists (>= 1 valid ray, every ray within 60 degrees of the first)
-    f3 c00, e1, e2;   // corner direction a + x0 e1 + y0 e2 and the frame's tangents
-    float dx, dy;     // x1 - x0, y1 - y0
-};
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = fminf(v, __shfl_xor(v, m, 64));
-    return v;
-}
-__device__ __forceinline__ float uniform(float v) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v))); }
-// (up to two rays per lane: the pixel pair of the half-tile waves, one ray of the quarter-tile waves with valid1 = false)
-__device__ __forceinline__ WavePyramid wave_pyramid(bool valid0, f3 d0, bool valid1, f3 d1) {
-    WavePyramid w;
-    w.on = false;
-    w.c00 = w.e1 = w.e2 = mk3(0.f, 0.f, 0.f);
-    w.dx = w.dy = 0.f;
-    const unsigned long long m0 = __ballot(valid0), m1 = __ballot(valid1);
-    if (!(m0 | m1)) return w;
-    f3 a;
-    if (m0) { const int src = __ffsll((long long)m0) - 1; a = mk3(__shfl(d0.x, src, 64), __shfl(d0.y, src, 64), __shfl(d0.z, src, 64)); }
-    else { const int src = __ffsll((long long)m1) - 1; a = mk3(__shfl(d1.x, src, 64), __shfl(d1.y, src, 64), __shfl(d1.z, src, 64)); }
-    a = a * __builtin_amdgcn_rsqf(dot(a, a));
-    a = mk3(uniform(a.x), uniform(a.y), uniform(a.z));
-    // any unit tangent pair: e1 = a x (the axis a is least aligned with), e2 = a x e1
-    const float ax = fabsf(a.x), ay = fabsf(a.y), az = fabsf(a.z);
-    const f3 k = (ax <= ay && ax <= az) ? mk3(1.f, 0.f, 0.f) : (ay <= az ? mk3(0.f, 1.f, 0.f) : mk3(0.f, 0.f, 1.f));
-    f3 e1 = cross(a, k);
-    e1 = e1 * __builtin_amdgcn_rsqf(dot(e1, e1));
-    const f3 e2 = cross(a, e1);
-    const float q0 = dot(d0, a), q1 = dot(d1, a);
-    const float l0 = __builtin_amdgcn_sqrtf(dot(d0, d0)), l1 = __builtin_amdgcn_sqrtf(dot(d1, d1));
-    const bool ok0 = !valid0 || q0 > 0.5f * l0, ok1 = !valid1 || q1 > 0.5f * l1;
-    if (!__all(ok0 && ok1)) return w;
-    const float big = 3.0e38f;
-    const float i0 = 1.f / q0, i1 = 1.f / q1;
-    const float x_0 = dot(d0, e1) * i0, y_0 = dot(d0, e2) * i0, x_1 = dot(d1, e1) * i1, y_1 = dot(d1, e2) * i1;
-    const float xlo = wave_min(fminf(valid0 ? x_0 : big, valid1 ? x_1 : big)), xhi = -wave_min(fminf(valid0 ? -x_0 : big, valid1 ? -x_1 : big));
-    const float ylo = wave_min(fminf(valid0 ? y_0 : big, valid1 ? y_1 : big)), yhi = -wave_min(fminf(valid0 ? -y_0 : big, valid1 ? -y_1 : big));
-    const float pad = 1e-6f;   // tangent units (a pixel is ~1e-3): the rounding of x, y themselves
-    const float x0 = uniform(xlo) - pad, x1 = uniform(xhi) + pad, y0 = uniform(ylo) - pad, y1 = uniform(yhi) + pad;
-    w.on = true;
-    w.c00 = a + e1 * x0 + e2 * y0;
-    w.e1 = mk3(uniform(e1.x), uniform(e1.y), uniform(e1.z));
-    w.e2 = mk3(uniform(e2.x), uniform(e2.y), uniform(e2.z));
-    w.c00 = mk3(uniform(w.c00.x), uniform(w.c00.y), uniform(w.c00.z));
-    w.dx = x1 - x0;
-    w.dy = y1 - y0;
-    return w;
-}
-__device__ __forceinline__ WavePyramid wave_pyramid(const RayPair& rp) {
-    return wave_pyramid(rp.valid0, mk3(rp.d.x.x, rp.d.y.x, rp.d.z.x), rp.valid1, mk3(rp.d.x.y, rp.d.y.y, rp.d.z.y));
-}
-// does the staged record's sphere miss every line of the wave?  (rec as stage_entry builds it, uniform-origin form: r5.xyz = u)
-__device__ __forceinline__ bool pyramid_misses(const WavePyramid& w, float4 r0, float4 r1, float4 r2, float gmax, float4 r5) {
-    const f3 m0 = mk3(r0.x, r0.y, r0.z), m1 = mk3(r1.x, r1.y, r1.z), m2 = mk3(r2.x, r2.y, r2.z);
-    const f3 u = mk3(r5.x, r5.y, r5.z);
-    const f3 v00 = mk3(dot(m0, w.c00), dot(m1, w.c00), dot(m2, w.c00));
-    const f3 f1 = mk3(dot(m0, w.e1), dot(m1, w.e1), dot(m2, w.e1)), f2 = mk3(dot(m0, w.e2), dot(m1, w.e2), dot(m2, w.e2));
-    const f3 v10 = v00 + f1 * w.dx, v01 = v00 + f2 * w.dy;
-    const float rr = 1.001f * __builtin_amdgcn_sqrtf(gmax) + 1e-5f * __builtin_amdgcn_sqrtf(dot(u, u));
-    const float r2lim = rr * rr;
-    // signed distance of the sphere's centre (the origin) OUT of the face, times |n|:  s = -(u . n_out)
-    const f3 nx0 = cross(v00, f2), nx1 = cross(v10, f2), ny0 = cross(v00, f1), ny1 = cross(v01, f1), wf = cross(f1, f2);
-    const float sx0 = -dot(u, nx0), sx1 = dot(u, nx1), sy0 = dot(u, ny0), sy1 = -dot(u, ny1), sf = -dot(u, wf);
-    const bool front = sf > 0.f && sf * sf > r2lim * dot(wf, wf);
-    const bool out = (sx0 > 0.f && sx0 * sx0 > r2lim * dot(nx0, nx0)) || (sx1 > 0.f && sx1 * sx1 > r2lim * dot(nx1, nx1)) ||
-                     (sy0 > 0.f && sy0 * sy0 > r2lim * dot(ny0, ny0)) || (sy1 > 0.f && sy1 * sy1 > r2lim * dot(ny1, ny1));
-    return front && out;
-}
-
-// canonical-frame ray of the pixel pair against one staged entry, and the accept test
-struct PairGeom {
-    p3 u, v;        // canonical origin, canonical (un-normalised) direction
-    v2f l2, cc;     // |v|^2, |v x u|^2  (grayDist = cc / l2)
-    bool acc0, acc1;
-};
-template <bool UNI>
-__device__ __forceinline__ PairGeom pair_geometry(const RayPair& rp, const float4* __restrict__ rec) {
-    const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
-    PairGeom g;
-    const f3 m0 = mk3(r0.x, r0.y, r0.z), m1 = mk3(r1.x, r1.y, r1.z), m2 = mk3(r2.x, r2.y, r2.z);
-    g.v = p3{pdot(m0, rp.d), pdot(m1, rp.d), pdot(m2, rp.d)};
-    if (UNI) {
-        const float4 r5 = rec[5];
-        g.u = p3{splat(r5.x), splat(r5.y), splat(r5.z)};
-    } else {
-        const p3 dl = p3{rp.o.x - r0.w, rp.o.y - r1.w, rp.o.z - r2.w};
-        g.u = p3{pdot(m0, dl), pdot(m1, dl), pdot(m2, dl)};
-    }
-    g.l2 = pdot(g.v, g.v);
-    const p3 c = pcross(g.v, g.u);
-    g.cc = pdot(c, c);
-    const v2f lim = rec[4].w * g.l2;
-    g.acc0 = g.cc.x < lim.x;
-    g.acc1 = g.cc.y < lim.y;
-    return g;
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// Experiment (round 5, -DGRUT_FWD_MFMA=1): the canonical direction v = M d of the pair geometry on the matrix pipe.
-// v_mfma_f32_4x4x1_16b_f32 multiplies, in each of 16 blocks of four lanes, a 4 x 1 column (A: one value per lane, row = lane & 3) with a
-// 1 x 4 row (B: one value per lane, column = lane & 3) and adds the 4 x 4 product to the accumulator (register r of a lane = row r of its
-// column).  With A = a coefficient of M of staged entry (group + (lane & 3)) and B = the lane's own ray direction component, register r
-// of every lane receives coefficient(entry group + r) x d(own pixel): three chained instructions (z, y, x - the order of pdot) give one
-// component of v for FOUR entries; fp32 MFMA is an exact fmaf chain on gfx950, so the bits are pdot's.  18 instructions per group of four
-// entries and pixel pair replace 4 x 9 packed multiply-adds on the VALU pipe; the accumulators of the next group are issued before the
-// current group is composited.
-// ---------------------------------------------------------------------------------------------
-#ifndef GRUT_FWD_MFMA
-#define GRUT_FWD_MFMA 0
-#endif
-typedef float v4f __attribute__((ext_vector_type(4)));
-struct GroupV {
-    v4f x0, x1, y0, y1, z0, z1;   // component of v, pixel of the pair; register r = entry group + r
-};
-__device__ __forceinline__ GroupV group_directions(const RayPair& rp, const float4* __restrict__ s_rec, int jg, int lane) {
-    const float4* rec = &s_rec[(jg + (lane & 3)) * kRecQuads];
-    const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
-    const v4f zero = {0.f, 0.f, 0.f, 0.f};
-    GroupV g;
-    g.x0 = __builtin_amdgcn_mfma_f32_4x4x1f32(r0.z, rp.d.z.x, zero, 0, 0, 0);
-    g.x1 = __builtin_amdgcn_mfma_f32_4x4x1f32(r0.z, rp.d.z.y, zero, 0, 0, 0);
-    g.y0 = __builtin_amdgcn_mfma_f32_4x4x1f32(r1.z, rp.d.z.x, zero, 0, 0, 0);
-    g.y1 = __builtin_amdgcn_mfma_f32_4x4x1f32(r1.z, rp.d.z.y, zero, 0, 0, 0);
-    g.z0 = __builtin_amdgcn_mfma_f32_4x4x1f32(r2.z, rp.d.z.x, zero, 0, 0, 0);
-    g.z1 = __builtin_amdgcn_mfma_f32_4x4x1f32(r2.z, rp.d.z.y, zero, 0, 0, 0);
-    g.x0 = __builtin_amdgcn_mfma_f32_4x4x1f32(r0.y, rp.d.y.x, g.x0, 0, 0, 0);
-    g.x1 = __builtin_amdgcn_mfma_f32_4x4x1f32(r0.y, rp.d.y.y, g.x1, 0, 0, 0);
-    g.y0 = __builtin_amdgcn_mfma_f32_4x4x1f32(r1.y, rp.d.y.x, g.y0, 0, 0, 0);
-    g.y1 = __builtin_amdgcn_mfma_f32_4x4x1f32(r1.y, rp.d.y.y, g.y1, 0, 0, 0);
-    g.z0 = __builtin_amdgcn_mfma_f32_4x4x1f32(r2.y, rp.d.y.x, g.z0, 0, 0, 0);
-    g.z1 = __builtin_amdgcn_mfma_f32_4x4x1f32(r2.y, rp.d.y.y, g.z1, 0, 0, 0);
-    g.x0 = __builtin_amdgcn_mfma_f32_4x4x1f32(r0.x, rp.d.x.x, g.x0, 0, 0, 0);
-    g.x1 = __builtin_amdgcn_mfma_f32_4x4x1f32(r0.x, rp.d.x.y, g.x1, 0, 0, 0);
-    g.y0 = __builtin_amdgcn_mfma_f32_4x4x1f32(r1.x, rp.d.x.x, g.y0, 0, 0, 0);
-    g.y1 = __builtin_amdgcn_mfma_f32_4x4x1f32(r1.x, rp.d.x.y, g.y1, 0, 0, 0);
-    g.z0 = __builtin_amdgcn_mfma_f32_4x4x1f32(r2.x, rp.d.x.x, g.z0, 0, 0, 0);
-    g.z1 = __builtin_amdgcn_mfma_f32_4x4x1f32(r2.x, rp.d.x.y, g.z1, 0, 0, 0);
-    return g;
-}
-// the rest of pair_geometry<true> for a direction that is already there
-__device__ __forceinline__ PairGeom pair_geometry_given_v(p3 v, const float4* __restrict__ rec) {
-    PairGeom g;
-    g.v = v;
-    const float4 r5 = rec[5];
-    g.u = p3{splat(r5.x), splat(r5.y), splat(r5.z)};
-    g.l2 = pdot(g.v, g.v);
-    const p3 c = pcross(g.v, g.u);
-    g.cc = pdot(c, c);
-    const v2f lim = rec[4].w * g.l2;
-    g.acc0 = g.cc.x < lim.x;
-    g.acc1 = g.cc.y < lim.y;
-    return g;
-}
-
-// particle_response<DEG> for a pixel pair (one v_exp_f32 per pixel, the polynomial part packed)
-template <int DEG>
-__device__ __forceinline__ v2f pair_response(v2f g) {
-    constexpr float kLog2e = 1.4426950408889634f;
-    if constexpr (DEG == 2) {
-        const v2f e = g * (-0.5f * kLog2e);
-        return v2f{__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
-    } else if constexpr (DEG == 4) {
-        const v2f e = (g * g) * (-0.0555555555556f * kLog2e);
-        return v2f{__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
-    } else {
-        return v2f{particle_response<DEG>(g.x), particle_response<DEG>(g.y)};
-    }
-}
-
-// the [H,W,4] image: fp32, or IEEE half with FEATURE_OUTPUT_HALF (rayPayload.cuh:176-186 writes __float2half of every component;
-// rayPayloadBackward.cuh:50-58 reads them back)
-__device__ __forceinline__ void store_fd(const GutParams& P, float4* __restrict__ out_fd, size_t pix, float4 o) {
-    if (P.out_half) {
-        __half* h = reinterpret_cast<__half*>(out_fd) + 4 * pix;
-        h[0] = __float2half(o.x); h[1] = __float2half(o.y); h[2] = __float2half(o.z); h[3] = __float2half(o.w);
-    } else {
-        out_fd[pix] = o;
-    }
-}
-__device__ __forceinline__ float4 load_fd(const GutParams& P, const float4* __restrict__ fd, size_t pix) {
-    if (P.out_half) {
-        const __half* h = reinterpret_cast<const __half*>(fd) + 4 * pix;
-        return make_float4(__half2float(h[0]), __half2float(h[1]), __half2float(h[2]), __half2float(h[3]));
-    }
-    return fd[pix];
-}
-// the plugin's `pred_features` / `pred_opacity` as contiguous tensors of their own (GutFrame::out_features / out_opacity)
-__device__ __forceinline__ void write_split_outputs(const GutParams& P, size_t pix, float4 o) {
-    if (P.out_features) { P.out_features[3 * pix] = o.x; P.out_features[3 * pix + 1] = o.y; P.out_features[3 * pix + 2] = o.z; }
-    if (P.out_opacity) P.out_opacity[pix] = o.w;
-}
-
-// ---------------------------------------------------------------------------------------------
 // K7: compositing forward — GUTKBufferRenderer::evalKBuffer, K = 0 (gutKBufferRenderer.cuh:273-352)
 // Rounds are aligned to multiples of 64 in the global sorted list, so every segment boundary (multiple of
 // kGutSegment) is a round start, where the running state is checkpointed for the gradient sweep.
 // ---------------------------------------------------------------------------------------------
-#ifndef GRUT_FWD_PRIO
-#define GRUT_FWD_PRIO 0   // K > 0: s_setprio 1 / 2 / 3 after K / 2 K / 3 K composited rounds of 64 entries (see render_fwd_sweep)
-#endif
 #ifndef GRUT_FWD_HALF_TILE_CULL
 #define GRUT_FWD_HALF_TILE_CULL 1   // staged entries whose sphere misses the wave's ray pyramid are dropped (see WavePyramid)
 #endif
@@ -477,7 +57,6 @@ __device__ __forceinline__ void render_fwd_sweep(const GutParams& P, const RayPa
     const unsigned long long t_sweep = COUNT ? wall_clock64() : 0ull;
     unsigned long long t_first = 0ull, t_stage = 0ull;
     uint32_t b = range.x;
-    uint32_t n_prio = 0u;   // GRUT_FWD_PRIO
     RawEntry next = load_entry<false>(b + lane, min(range.y, (b & ~63u) + 64u), lists, density12, rgb);
     constexpr bool CULL = GRUT_FWD_HALF_TILE_CULL != 0;
     WavePyramid pyr;
@@ -517,57 +96,6 @@ __device__ __forceinline__ void render_fwd_sweep(const GutParams& P, const RayPa
         if (COUNT) t_stage += wall_clock64() - t_round;
         // fetch the following round while this one is being composited
         next = load_entry<false>(bend + lane, min(range.y, bend + 64u), lists, density12, rgb);
-#if GRUT_FWD_MFMA
-        if constexpr (UNI) {
-#if GRUT_FWD_MFMA == 1
-            GroupV gn = group_directions(rp, s_rec, 0, lane);
-#endif
-            bool stop = false;
-            for (int jg = 0; jg < n && !stop; jg += 4) {
-#if GRUT_FWD_MFMA == 1
-                const GroupV gv = gn;
-                if (jg + 4 < n) gn = group_directions(rp, s_rec, jg + 4, lane);   // in flight on the matrix pipe while this group is composited
-#else
-                const GroupV gv = group_directions(rp, s_rec, jg, lane);           // (2: no group ahead - 24 registers fewer; the other waves of the SIMD cover the latency)
-#endif
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int j = jg + r;
-                    if (j >= n) break;
-                    if (!__any(alive0 || alive1)) { stop = true; break; }
-                    const float4* rec = &s_rec[j * kRecQuads];
-                    const PairGeom g = pair_geometry_given_v(p3{v2f{gv.x0[r], gv.x1[r]}, v2f{gv.y0[r], gv.y1[r]}, v2f{gv.z0[r], gv.z1[r]}}, rec);
-                    const bool c0 = g.acc0 && alive0, c1 = g.acc1 && alive1;
-                    if (COUNT) ++n_eval;
-                    if (!__any(c0 || c1)) continue;
-                    if (COUNT) ++n_acc;
-                    const float4 r3 = rec[3], r4 = rec[4];
-                    const v2f il2 = prcp(g.l2);
-                    const v2f gray = g.cc * il2;
-                    const v2f resp = pair_response<DEG>(gray);
-                    const v2f ad = resp * r3.w;
-                    // hit distance |S n (n.-u)| = |v.u| |S v| / |v|^2   (gaussianParticles.slang:181-190)
-                    const v2f vu = pdot(g.v, g.u);
-                    const p3 sv = p3{r3.x * g.v.x, r3.y * g.v.y, r3.z * g.v.z};
-                    const v2f ss = pdot(sv, sv) * (vu * vu);
-                    const v2f hitT = v2f{__builtin_amdgcn_sqrtf(ss.x), __builtin_amdgcn_sqrtf(ss.y)} * il2;
-                    const bool h0 = c0 && (hitT.x > rp.tmin.x) && (hitT.x < rp.tmax.x);
-                    const bool h1 = c1 && (hitT.y > rp.tmin.y) && (hitT.y < rp.tmax.y);
-                    const v2f alpha = psel(h0, h1, v2f{fminf(P.max_alpha, ad.x), fminf(P.max_alpha, ad.y)}, splat(0.f));
-                    const v2f hT = psel(h0, h1, hitT, splat(0.f));
-                    const v2f w = alpha * T;
-                    D = pfma(hT, w, D);
-                    T = T * (1.f - alpha);
-                    Cr = pfma(r4.x, w, Cr);
-                    Cg = pfma(r4.y, w, Cg);
-                    Cb = pfma(r4.z, w, Cb);
-                    cnt += psel(w.x > 0.f, w.y > 0.f, splat(1.f), splat(0.f));
-                    alive0 = alive0 && !(T.x < P.min_transmittance);
-                    alive1 = alive1 && !(T.y < P.min_transmittance);
-                }
-            }
-        } else
-#endif
         for (int j = 0; j < n; ++j) {
             if (!__any(alive0 || alive1)) break;   // the rest of the round is behind every pixel's termination
             const float4* rec = &s_rec[j * kRecQuads];
@@ -602,15 +130,6 @@ __device__ __forceinline__ void render_fwd_sweep(const GutParams& P, const RayPa
         }
         __syncthreads();
         b = bend;
-#if GRUT_FWD_PRIO > 0
-        // a wave that has already composited many rounds is one of the launch's long ones (the lifetimes follow the accepted entries, which
-        // nothing known before the launch predicts): it takes issue priority over the younger waves of its SIMD, so the long waves end
-        // earlier and the launch's ramp-down shortens
-        ++n_prio;
-        if (n_prio == 1u * GRUT_FWD_PRIO) __builtin_amdgcn_s_setprio(1);
-        else if (n_prio == 2u * GRUT_FWD_PRIO) __builtin_amdgcn_s_setprio(2);
-        else if (n_prio == 3u * GRUT_FWD_PRIO) __builtin_amdgcn_s_setprio(3);
-#endif
     }
     st = FwdState{T, D, Cr, Cg, Cb, cnt, 0ull};
     if (COUNT && P.work && lane == 0) {   // per-wave words, summed on the host (atomics on two shared counters would serialise the waves' exits)
@@ -964,7 +483,6 @@ __device__ __forceinline__ void render_bwd_sweep(const GutParams& P, const RayPa
                 for (int k = 0; k < 16; ++k) extra[k] = 0.f;
                 extra[0] = sXm.x.x + sXm.x.y; extra[1] = sXm.y.x + sXm.y.y; extra[2] = sXm.z.x + sXm.z.y;
             }
-#if GRUT_BWD_FULL_REDUCE == 2
             // transpose through LDS instead of the DPP butterfly: the sweep is bound by VALU issue and the LDS pipe is idle, so the
             // 16 x 64 -> 16 reduction is moved there: every lane parks its 16 terms (term-major, rows padded to 65 words: conflict-free
             // both ways), lane l then sums 16 of the 64 values of term l & 15 and two lane-swap steps add the four quarters
@@ -989,20 +507,6 @@ __device__ __forceinline__ void render_bwd_sweep(const GutParams& P, const RayPa
                 const float tot2 = wave_reduce_scatter16_all(extra, lane);
                 if (lane < 16) s_acc2[j * 16 + lane] = tot2;
             }
-#elif GRUT_BWD_FULL_REDUCE
-            // every lane ends with the wave total of term l & 15 (in-row DPP butterfly, then two lane-swap steps across the rows);
-            // one row of 16 lanes parks the totals of the entry in LDS for the flush
-            const float tot = wave_reduce_scatter16_all(terms, lane);
-            if (lane < 16) s_acc[j * 16 + lane] = tot;
-            if (HAS_GDIST) {
-                const float tot2 = wave_reduce_scatter16_all(extra, lane);
-                if (lane < 16) s_acc2[j * 16 + lane] = tot2;
-            }
-#else
-            // lane l ends with the sum over its 16-lane row of term l & 15; the four rows are added by the flush
-            s_acc[j * 64 + lane] = wave_reduce_scatter16_rows(terms, lane);
-            if (HAS_GDIST) s_acc2[j * 64 + lane] = wave_reduce_scatter16_rows(extra, lane);
-#endif
             T = nextT;
             iT = inextT_raw;
             alive0 = alive0 && !(T.x < P.min_transmittance);
@@ -1013,19 +517,8 @@ __device__ __forceinline__ void render_bwd_sweep(const GutParams& P, const RayPa
         if (lane < (int)kBatch && ((hit_entries >> lane) & 1u)) {
             const float4* rec = &s_rec[lane * kRecQuads];
             const uint32_t pos = __float_as_uint(rec[5].w);
-#if GRUT_BWD_FULL_REDUCE
             const float4* acc = reinterpret_cast<const float4*>(&s_acc[lane * 16]);
             float4 a0 = acc[0], a1 = acc[1], a2 = acc[2], a3 = acc[3];
-#else
-            const float4* acc = reinterpret_cast<const float4*>(&s_acc[lane * 64]);
-            float4 a0 = acc[0], a1 = acc[1], a2 = acc[2], a3 = acc[3];
-#pragma unroll
-            for (int r = 1; r < 4; ++r) {
-                const float4 b0 = acc[4 * r], b1 = acc[4 * r + 1], b2 = acc[4 * r + 2], b3 = acc[4 * r + 3];
-                a0.x += b0.x; a0.y += b0.y; a0.z += b0.z; a0.w += b0.w; a1.x += b1.x; a1.y += b1.y; a1.z += b1.z; a1.w += b1.w;
-                a2.x += b2.x; a2.y += b2.y; a2.z += b2.z; a2.w += b2.w; a3.x += b3.x; a3.y += b3.y; a3.z += b3.z; a3.w += b3.w;
-            }
-#endif
             if (!HAS_GDIST && UNI) {  // complete M = (sum B) (x) (o - mu) - sum (t B) (x) d
                 const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
                 const f3 dl = rp.origin - mk3(r0.w, r1.w, r2.w);
@@ -1036,15 +529,7 @@ __device__ __forceinline__ void render_bwd_sweep(const GutParams& P, const RayPa
             const size_t slot = 2 * (size_t)pos + half;
             float4* out = reinterpret_cast<float4*>(slots.partial + slot * (HAS_GDIST ? 20 : 16));
             out[0] = a0; out[1] = a1; out[2] = a2; out[3] = a3;
-            if (HAS_GDIST) {
-                float ex = 0.f, ey = 0.f, ez = 0.f;
-#if GRUT_BWD_FULL_REDUCE
-                ex = s_acc2[lane * 16]; ey = s_acc2[lane * 16 + 1]; ez = s_acc2[lane * 16 + 2];
-#else
-                for (int r = 0; r < 4; ++r) { ex += s_acc2[lane * 64 + 16 * r]; ey += s_acc2[lane * 64 + 16 * r + 1]; ez += s_acc2[lane * 64 + 16 * r + 2]; }
-#endif
-                out[4] = make_float4(ex, ey, ez, 0.f);
-            }
+            if (HAS_GDIST) out[4] = make_float4(s_acc2[lane * 16], s_acc2[lane * 16 + 1], s_acc2[lane * 16 + 2], 0.f);
             slots.flag[slot] = 1;
         }
         __syncthreads();
@@ -1067,18 +552,9 @@ __global__ __launch_bounds__(64) void gut_render_bwd_kernel(
                                                             GutGradSlots slots, GutCheckpoints ck) {
     constexpr uint32_t kBatch = kBwdBatch;
     __shared__ float4 s_rec[kBatch * kRecQuads];
-#if GRUT_BWD_FULL_REDUCE == 2
     __shared__ float s_tr[16 * 65];                            // transposition buffer of the per-entry reduction
-#else
-    float* s_tr = nullptr;
-#endif
-#if GRUT_BWD_FULL_REDUCE
     __shared__ float s_acc[kBatch * 16];                       // per staged entry: the wave totals of its 16 terms
     __shared__ float s_acc2[HAS_GDIST ? kBatch * 16 : 1];      // depth-gradient extras (3 terms used)
-#else
-    __shared__ float s_acc[kBatch * 64];                       // per staged entry: 16 terms x 4 row partials
-    __shared__ float s_acc2[HAS_GDIST ? kBatch * 64 : 1];      // depth-gradient extras (3 terms used)
-#endif
     // task = (virtual tile, half).  Virtual tiles [0, bndPad) are the segments that start at segment boundary b (sorted
     // index b * kGutSegment): they are the long, dense tasks and are dispatched first so that the tail of the launch
     // is made of the short first segments of each tile list, virtual tiles [bndPad, bndPad + tiles).  Only a quarter of the
@@ -1093,15 +569,12 @@ __global__ __launch_bounds__(64) void gut_render_bwd_kernel(
     uint32_t tile, seg_begin;
     bool from_checkpoint = false;
     uint32_t boundary = 0, reached_bits = 3u;   // bit q: quarter q of the half tile (pixel .x / .y of the lanes) arrived at the boundary alive
-#ifndef GRUT_BWD_TASK_STRIDE
-#define GRUT_BWD_TASK_STRIDE 0   // (a strided order of the gradient sweep's tasks was measured slower: 0.854-0.863 vs 0.839 ms)
-#endif
     if (vtile >= bnd_pad) {
         tile = vtile - bnd_pad;
         if (tile >= num_tiles) return;
         seg_begin = ranges[tile].x;
     } else {
-        boundary = GRUT_BWD_TASK_STRIDE > 1 ? stride_permute(vtile, bnd_pad, GRUT_BWD_TASK_STRIDE) : vtile;
+        boundary = vtile;
         if (boundary == 0 || boundary >= ck.num_boundaries) return;
         reached_bits = ck.reached[(size_t)boundary * 2 + half];
         if (!reached_bits) return;                                   // the forward sweep never got here alive
@@ -1160,466 +633,8 @@ __global__ __launch_bounds__(64) void gut_render_bwd_kernel(
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// K > 0 ("sorted") compositing — HitParticleKBufferT<K> + evalKBuffer (gutKBufferRenderer.cuh:62-122, 273-352) and its
-// backward processHitParticle<Backward> (:158-198; Slang reverse mode of the back-to-front lerp form,
-// shRadiativeParticles.slang:210-256, gaussianParticles.slang:420-479).
-// Every pixel keeps the K nearest pending hits (by hitT) in registers and composites the nearest one when the buffer is
-// full, so neighbouring pixels pop DIFFERENT particles at the same step: there is nothing to reduce across the wave, and
-// the gradient is accumulated per hit with atomics exactly like the reference does in this mode.  One pixel per lane,
-// one wave64 per 16x4 strip; correctness-first kernel (the unsorted K = 0 path above is the tuned one).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float gray_limit_rt(int deg, float x) {
-    switch (deg) {
-    case 8: return response_gray_limit<8>(x);
-    case 5: return response_gray_limit<5>(x);
-    case 4: return response_gray_limit<4>(x);
-    case 3: return response_gray_limit<3>(x);
-    case 1: return response_gray_limit<1>(x);
-    case 0: return response_gray_limit<0>(x);
-    default: return response_gray_limit<2>(x);
-    }
-}
-__device__ __forceinline__ float response_rt(int deg, float g) {
-    switch (deg) {
-    case 8: return particle_response<8>(g);
-    case 5: return particle_response<5>(g);
-    case 4: return particle_response<4>(g);
-    case 3: return particle_response<3>(g);
-    case 1: return particle_response<1>(g);
-    case 0: return particle_response<0>(g);
-    default: return particle_response<2>(g);
-    }
-}
-__device__ __forceinline__ float response_grd_rt(int deg, float g, float gres, float gresGrd) {
-    switch (deg) {
-    case 8: return particle_response_grd<8>(g, gres, gresGrd);
-    case 5: return particle_response_grd<5>(g, gres, gresGrd);
-    case 4: return particle_response_grd<4>(g, gres, gresGrd);
-    case 3: return particle_response_grd<3>(g, gres, gresGrd);
-    case 1: return particle_response_grd<1>(g, gres, gresGrd);
-    case 0: return particle_response_grd<0>(g, gres, gresGrd);
-    default: return particle_response_grd<2>(g, gres, gresGrd);
-    }
-}
-
-// Sorted mode: the k-buffer ORDERS a ray's hits by their fp32 hit distance, so two implementations agree on the order only if they agree on
-// the distance's bits.  The hit distance of an accepted hit is therefore evaluated in the CHECKER's operation order (the checker's gut_oracle.c:
-// density_hit_ex, itself the source order of gaussianParticles.slang:96-110, 181-190): every product and sum rounded on its own, correctly
-// rounded 1/x and sqrt - ~70 instructions per ACCEPTED hit on top of the accept test, which keeps the fast pre-transformed form (its flips
-// are identified per pixel by the parity tests; an order tie could not be).  rt* = rows of R^T from the quaternion, gis = 1 / scale.
-__device__ __forceinline__ float sub_rn(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ void rn_rotT(float r, float x, float y, float z, f3& r0, f3& r1, f3& r2) {   // quat_wxyz_to_rotT, uncontracted
-    const float xx = mul_rn(x, x), yy = mul_rn(y, y), zz = mul_rn(z, z), xy = mul_rn(x, y), xz = mul_rn(x, z), yz = mul_rn(y, z);
-    const float rx = mul_rn(r, x), ry = mul_rn(r, y), rz = mul_rn(r, z);
-    r0 = mk3(sub_rn(1.f, mul_rn(2.f, add_rn(yy, zz))), mul_rn(2.f, add_rn(xy, rz)), mul_rn(2.f, sub_rn(xz, ry)));
-    r1 = mk3(mul_rn(2.f, sub_rn(xy, rz)), sub_rn(1.f, mul_rn(2.f, add_rn(xx, zz))), mul_rn(2.f, add_rn(yz, rx)));
-    r2 = mk3(mul_rn(2.f, add_rn(xz, ry)), mul_rn(2.f, sub_rn(yz, rx)), sub_rn(1.f, mul_rn(2.f, add_rn(xx, yy))));
-}
-__device__ __forceinline__ float oracle_order_hit_t(const Ray& ray, f3 pos, f3 scl, f3 rt0, f3 rt1, f3 rt2, f3 gis) {
-    const f3 gposc = mk3(sub_rn(ray.o.x, pos.x), sub_rn(ray.o.y, pos.y), sub_rn(ray.o.z, pos.z));
-    const f3 gro = mk3(mul_rn(gis.x, rn_dot3(rt0, gposc)), mul_rn(gis.y, rn_dot3(rt1, gposc)), mul_rn(gis.z, rn_dot3(rt2, gposc)));
-    const f3 grdu = mk3(mul_rn(gis.x, rn_dot3(rt0, ray.d)), mul_rn(gis.y, rn_dot3(rt1, ray.d)), mul_rn(gis.z, rn_dot3(rt2, ray.d)));
-    const float inv = 1.f / sqrtf(rn_dot3(grdu, grdu));            // (IEEE division and square root: the file is not built with fast-math)
-    const f3 grd = mk3(mul_rn(grdu.x, inv), mul_rn(grdu.y, inv), mul_rn(grdu.z, inv));
-    const float along = rn_dot3(grd, mk3(-gro.x, -gro.y, -gro.z));
-    const f3 grds = mk3(mul_rn(scl.x, mul_rn(grd.x, along)), mul_rn(scl.y, mul_rn(grd.y, along)), mul_rn(scl.z, mul_rn(grd.z, along)));
-    return sqrtf(rn_dot3(grds, grds));
-}
-
-template <int K>
-struct KBuffer {   // ascending in hitT: slot 0 = nearest pending hit, empty slots hold hitT = -1 at the front
-    float hitT[K], alpha[K];
-    uint32_t idx[K];
-    int num;
-    __device__ __forceinline__ void clear() {
-        num = 0;
-#pragma unroll
-        for (int i = 0; i < K; ++i) { hitT[i] = -1.f; alpha[i] = 0.f; idx[i] = 0xFFFFFFFFu; }
-    }
-    // HitParticleKBufferT::insert (:76-91); the caller has already consumed slot 0 when the buffer was full
-    // branch-free: the keys move with min / max (no swap on equal keys, like the reference's strict `>`), the payloads
-    // with selects
-    __device__ __forceinline__ void insert(float t, float a, uint32_t id) {
-#pragma unroll
-        for (int i = K - 1; i >= 0; --i) {
-            const bool up = t > hitT[i];
-            const float lo = fminf(t, hitT[i]), hi = fmaxf(t, hitT[i]);
-            const float aa = up ? alpha[i] : a;
-            const uint32_t ii = up ? idx[i] : id;
-            alpha[i] = up ? a : alpha[i];
-            idx[i] = up ? id : idx[i];
-            hitT[i] = hi;
-            t = lo; a = aa; id = ii;
-        }
-    }
-};
-
-struct KFwdState {
-    float T, D, Cr, Cg, Cb, cnt;
-};
-struct KBwdState {
-    float T;                 // forward running transmittance (termination only)
-    float Tb, Db, gT, gD;    // "behind" values and running upstream gradients
-    f3 Cb, gC;
-};
-
-__device__ __forceinline__ void k_process_fwd(const GutParams& P, const float* __restrict__ rgb, float hitT, float alpha, uint32_t idx,
-                                              KFwdState& s, bool& alive) {
-    const float w = alpha * s.T;
-    s.D = fmaf(hitT, w, s.D);
-    s.T *= (1.f - alpha);
-    if (w > 0.f) {
-        s.Cr = fmaf(fmaxf(rgb[3 * (size_t)idx], 0.f), w, s.Cr);
-        s.Cg = fmaf(fmaxf(rgb[3 * (size_t)idx + 1], 0.f), w, s.Cg);
-        s.Cb = fmaf(fmaxf(rgb[3 * (size_t)idx + 2], 0.f), w, s.Cb);
-        s.cnt += 1.f;
-    }
-    if (s.T < P.min_transmittance) alive = false;
-}
-
-// gradient of sum_ij (b_i e_j) rotT_ij(q) w.r.t. q = (r,x,y,z)  (matmul_bw_quat, mathUtils.cuh:458-521)
-__device__ __forceinline__ float4 quat_outer_contract(f3 b, f3 e, float4 q) {
-    const float r = 2.f * q.x, x = 2.f * q.y, y = 2.f * q.z, z = 2.f * q.w;
-    const float m00 = b.x * e.x, m01 = b.x * e.y, m02 = b.x * e.z, m10 = b.y * e.x, m11 = b.y * e.y, m12 = b.y * e.z, m20 = b.z * e.x,
-                m21 = b.z * e.y, m22 = b.z * e.z;
-    const float s01 = m01 + m10, s02 = m02 + m20, s12 = m12 + m21, a01 = m01 - m10, a02 = m20 - m02, a12 = m12 - m21;
-    return make_float4(z * a01 + y * a02 + x * a12, y * s01 + z * s02 + r * a12 - 2.f * x * (m11 + m22),
-                       x * s01 + z * s12 + r * a02 - 2.f * y * (m00 + m22), x * s02 + y * s12 + r * a01 - 2.f * z * (m00 + m11));
-}
-
-// One hit of one pixel in the sorted mode's backward: updates the running state and returns the hit's 14 gradient terms
-// (position 0-2, density 3, quaternion 4-7, scale 8-10, rgb 11-13) instead of adding them to memory; `k_bwd_flush` adds
-// them wave by wave.  Returns whether the hit contributed.
-__device__ __forceinline__ bool k_bwd_terms(const GutParams& P, const Ray& ray, const float4* __restrict__ density12, const float* __restrict__ rgb,
-                                            float hitT, float alpha, uint32_t idx, KBwdState& s, bool& alive, float (&terms)[16]) {
-    const bool contributes = alpha > 0.f;
-    if (contributes) {
-        const float w = __builtin_amdgcn_rcpf(1.f - alpha);
-        const f3 feat = mk3(fmaxf(rgb[3 * (size_t)idx], 0.f), fmaxf(rgb[3 * (size_t)idx + 1], 0.f), fmaxf(rgb[3 * (size_t)idx + 2], 0.f));
-        s.Cb = (s.Cb - feat * alpha) * w;
-        float dalpha = (feat.x - s.Cb.x) * s.gC.x + (feat.y - s.Cb.y) * s.gC.y + (feat.z - s.Cb.z) * s.gC.z;
-        terms[11] = alpha * s.gC.x; terms[12] = alpha * s.gC.y; terms[13] = alpha * s.gC.z;
-        s.gC = s.gC * (1.f - alpha);
-        s.Tb *= w;
-        s.Db = (s.Db - hitT * alpha) * w;
-        dalpha += (hitT - s.Db) * s.gD - s.Tb * s.gT;
-        const float ddepth = alpha * s.gD;
-        s.gD *= (1.f - alpha);
-        s.gT *= (1.f - alpha);
-
-        const float4 a = density12[3 * (size_t)idx], q = density12[3 * (size_t)idx + 1], sc = density12[3 * (size_t)idx + 2];
-        const m3 rotT = quat_wxyz_to_rotT(q.x, q.y, q.z, q.w);
-        const f3 gscl = mk3(sc.x, sc.y, sc.z), giscl = mk3(__builtin_amdgcn_rcpf(sc.x), __builtin_amdgcn_rcpf(sc.y), __builtin_amdgcn_rcpf(sc.z));
-        const f3 gposc = ray.o - mk3(a.x, a.y, a.z);
-        const f3 gposcr = mul_rows(rotT, gposc);
-        const f3 gro = giscl * gposcr;
-        const f3 rdr = mul_rows(rotT, ray.d);
-        const f3 grdu = giscl * rdr;
-        const float l2 = dot(grdu, grdu);
-        const float il = __builtin_amdgcn_rsqf(l2);
-        const f3 grd = grdu * il;
-        const f3 gcrod = cross(grd, gro);
-        const float gray = dot(gcrod, gcrod);
-        const float gres = response_rt(P.degree, gray);
-        float dres = 0.f, ddens = 0.f;  // reverse mode of min(MaxAlpha, .): only the smaller argument receives the gradient
-        if (gres * a.w < P.max_alpha) { dres = a.w * dalpha; ddens = gres * dalpha; }
-        const float grayGrd = response_grd_rt(P.degree, gray, gres, dres);
-        const float pdot = -dot(grd, gro);
-        const f3 grdd = grd * pdot;
-        const f3 grds = gscl * grdd;
-        const float gsq = dot(grds, grds);
-        const float gdist = __builtin_amdgcn_sqrtf(gsq);
-        const f3 grdsGrd = gsq > 0.f ? grds * (ddepth * __builtin_amdgcn_rcpf(gdist)) : mk3(0.f, 0.f, 0.f);
-        const f3 gsclHit = grdd * grdsGrd;
-        const float sdot = dot(grdsGrd * gscl, grd);
-        const f3 grdHit = gscl * grdsGrd * pdot - gro * sdot;
-        const f3 groHit = grd * (-sdot);
-        const f3 gcrodGrd = gcrod * (2.f * grayGrd);
-        const f3 grdGrd = mk3(gcrodGrd.z * gro.y - gcrodGrd.y * gro.z, gcrodGrd.x * gro.z - gcrodGrd.z * gro.x, gcrodGrd.y * gro.x - gcrodGrd.x * gro.y);
-        const f3 groGrd = mk3(gcrodGrd.y * grd.z - gcrodGrd.z * grd.y, gcrodGrd.z * grd.x - gcrodGrd.x * grd.z, gcrodGrd.x * grd.y - gcrodGrd.y * grd.x);
-        const f3 groTot = groGrd + groHit;
-        const f3 is2 = giscl * giscl;
-        const f3 gsclGro = mk3(-gposcr.x * is2.x, -gposcr.y * is2.y, -gposcr.z * is2.z) * groTot;
-        const f3 gposcrGrd = giscl * groTot;
-        const f3 gposcGrd = mul_cols(rotT, gposcrGrd);
-        const f3 dn = grdGrd + grdHit;
-        const f3 grduGrd = dn * il - grdu * (il * il * il * dot(dn, grdu));   // normalize backward
-        const f3 sclGrd = gsclHit + gsclGro + mk3(-rdr.x * is2.x, -rdr.y * is2.y, -rdr.z * is2.z) * grduGrd;
-        const float4 gq1 = quat_outer_contract(gposcrGrd, gposc, q), gq2 = quat_outer_contract(giscl * grduGrd, ray.d, q);
-        terms[0] = -gposcGrd.x; terms[1] = -gposcGrd.y; terms[2] = -gposcGrd.z; terms[3] = ddens;
-        terms[4] = gq1.x + gq2.x; terms[5] = gq1.y + gq2.y; terms[6] = gq1.z + gq2.z; terms[7] = gq1.w + gq2.w;
-        terms[8] = sclGrd.x; terms[9] = sclGrd.y; terms[10] = sclGrd.z;
-    }
-    s.T *= (1.f - alpha);
-    if (s.T < P.min_transmittance) alive = false;
-    return contributes;
-}
-// Adds the terms of the lanes with `have` to the gradient buffers: lanes that processed the SAME particle in this step
-// (neighbouring pixels usually do) are summed with a DPP reduce-scatter first, one set of 14 atomics per (wave, particle)
-// instead of one per (pixel, particle) — the reference's per-hit atomics (gutKBufferRenderer.cuh:158-198) cost this path
-// 147 ms per 1080p frame on MI355X.  (A further level — a per-wave LDS cache of per-particle totals across steps, evicted
-// to memory — was measured and dropped: 8.0 -> 9.6 ms; the atomics are not what bounds this kernel.)
-__device__ __forceinline__ void k_bwd_flush(bool have, uint32_t idx, const float (&terms)[16], int lane, float* __restrict__ g_density12,
-                                            float* __restrict__ g_rgb) {
-    unsigned long long m = __ballot(have);
-    while (m) {
-        const int leader = __ffsll((long long)m) - 1;
-        const uint32_t pid = (uint32_t)__builtin_amdgcn_readlane((int)idx, leader);
-        const bool part = have && (idx == pid);
-        float t[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t[k] = (part && k < 14) ? terms[k] : 0.f;
-        const float tot = wave_reduce_scatter16(t, lane);
-        if (lane < 11) atomicAdd(g_density12 + 12 * (size_t)pid + lane, tot);
-        else if (lane < 14) atomicAdd(g_rgb + 3 * (size_t)pid + (lane - 11), tot);
-        m &= ~__ballot(part);
-    }
-}
-
-// Round 5: the same sums through LDS instead of the DPP reduce-scatter (GRUT_K_FLUSH_LDS, default on).  A step's popping lanes hold
-// DIFFERENT particles more often than not (a pop is an OLD pending hit; neighbouring pixels' buffers drift apart), so the loop above runs
-// once per distinct particle at ~100 instructions each (16 selects + the 30-step reduce-scatter + the atomics).  Here every popping lane
-// parks its 14 terms in LDS (stride 15: conflict-free both ways) and lanes 0..13 ARE the 14 words of a particle's gradient: per distinct
-// particle the members' words are added from LDS (one read + one add per member) and leave as ONE atomic instruction - the hit-major
-// transposition of the 3DGRT replay backward (grt_replay_bwd_kernel).
-#ifndef GRUT_K_FLUSH_LDS
-#define GRUT_K_FLUSH_LDS 1
-#endif
-#ifndef GRUT_K_FLUSH_MINK
-#define GRUT_K_FLUSH_MINK 8    // smallest K that takes the LDS flush and the three-waves allocation that goes with it (K = 4 runs three waves
-                               // on the DPP reduce-scatter already; measured at 1 M / 1080p, step: K = 16 11.89 -> 10.90 ms, K = 8 8.89 -> 8.41 ms)
-#endif
-constexpr int kKTermStride = 15;
-__device__ __forceinline__ void k_bwd_flush_lds(bool have, uint32_t idx, const float (&terms)[16], int lane, float* __restrict__ s_terms,
-                                                float* __restrict__ g_density12, float* __restrict__ g_rgb) {
-    if (have) {
-#pragma unroll
-        for (int k = 0; k < 14; ++k) s_terms[lane * kKTermStride + k] = terms[k];
-    }
-    __syncthreads();   // single-wave workgroup: orders the LDS hand-off
-    unsigned long long m = __ballot(have);
-    float* const row = lane < 11 ? g_density12 + lane : g_rgb + (lane < 14 ? lane - 11 : 0);
-    const uint32_t stride = lane < 11 ? 12u : 3u;
-    while (m) {
-        const int leader = __ffsll((long long)m) - 1;
-        const uint32_t pid = (uint32_t)__builtin_amdgcn_readlane((int)idx, leader);
-        unsigned long long same = __ballot(have && idx == pid);
-        m &= ~same;
-        float v = 0.f;
-        while (same) {
-            const int s2 = __ffsll((long long)same) - 1;
-            same &= same - 1;
-            v += s_terms[s2 * kKTermStride + (lane < 14 ? lane : 0)];
-        }
-        if (lane < 14 && v != 0.f) atomicAdd(row + (size_t)pid * stride, v);
-    }
-    __syncthreads();   // the next step overwrites s_terms.  (Two buffers used alternately - one barrier per step - were measured SLOWER: 15.9 KB of
-                       // LDS per wave leave room for 10 waves per CU, i.e. two per SIMD again: backward 9.5 instead of 7.6 ms.)
-}
-
-template <int K, bool BWD>
-__device__ __forceinline__ void gut_render_k_body(const GutParams& P, const uint2* __restrict__ ranges, const EntryLists& lists,
-                                                  const float4* __restrict__ density12, const float* __restrict__ rgb,
-                                                  const float* __restrict__ ray_o, const float* __restrict__ ray_d,
-                                                  float4* __restrict__ out_fd, float* __restrict__ out_dist, float* __restrict__ out_cnt,
-                                                  const float4* __restrict__ g_fd, const float* __restrict__ g_dist,
-                                                  float* __restrict__ g_density12, float* __restrict__ g_rgb) {
-    constexpr int kQ = 8;   // quads per staged entry: 0-2 M rows | pos, 3 scale | density, 4 particle | accept limit, 5-7 rows of R^T | 1 / scale
-    __shared__ float4 s_rec[64 * kQ];
-    constexpr bool kLdsFlush = BWD && GRUT_K_FLUSH_LDS && K >= GRUT_K_FLUSH_MINK;
-    __shared__ float s_kterms[kLdsFlush ? 64 * kKTermStride : 1];
-    // strip -> (tile, strip-in-tile) with all four strips of a tile on one XCD
-    const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
-    const uint32_t tile = ((slot >> 2) << 3) + xcd, strip = slot & 3u;
-    if (tile >= (uint32_t)(P.gx * P.gy)) return;
-    const int lane = threadIdx.x;
-    const int px = (int)(tile % P.gx) * 16 + (lane & 15);
-    const int py = (int)(tile / P.gx) * 16 + (int)strip * 4 + (lane >> 4);
-    const Ray ray = init_ray(P, ray_o, ray_d, px, py);
-    bool alive = ray.valid;
-    const size_t pix = ray.valid ? (size_t)py * P.W + px : 0;
-    KFwdState fs{1.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    KBwdState bs;
-    bs.T = 1.f; bs.Tb = 0.f; bs.Db = 0.f; bs.gT = 0.f; bs.gD = 0.f; bs.Cb = mk3(0.f, 0.f, 0.f); bs.gC = mk3(0.f, 0.f, 0.f);
-    if (BWD && alive) {   // initializeBackwardRay (rayPayloadBackward.cuh:30-73); out_* hold the forward results here
-        const float4 f = load_fd(P, out_fd, pix), g = g_fd[pix];
-        bs.Cb = mk3(f.x, f.y, f.z); bs.gC = mk3(g.x, g.y, g.z);
-        bs.Tb = 1.f - f.w; bs.gT = -g.w;
-        bs.Db = out_dist[pix]; bs.gD = g_dist ? g_dist[pix] : 0.f;
-    }
-    KBuffer<K> kb;
-    kb.clear();
-    const uint2 range = ranges[tile];
-    for (uint32_t b = range.x; b < range.y; b += 64) {
-        if (!__any(alive)) break;
-        {   // stage up to 64 entries
-            const RawEntry e = load_entry(b + lane, range.y, lists, density12, rgb);
-            float4 r0 = make_float4(1.f, 0.f, 0.f, 0.f), r1 = make_float4(0.f, 1.f, 0.f, 0.f), r2 = make_float4(0.f, 0.f, 1.f, 0.f);
-            float4 r3 = make_float4(1.f, 1.f, 1.f, 0.f), r4 = make_float4(__uint_as_float(0xFFFFFFFFu), 0.f, 0.f, 0.f);
-            float4 r5 = r0, r6 = r1, r7 = r2;
-            if (e.idx != 0xFFFFFFFFu) {
-                {   // the hit-distance inputs in the checker's operation order (oracle_order_hit_t)
-                    f3 t0, t1, t2;
-                    rn_rotT(e.q.x, e.q.y, e.q.z, e.q.w, t0, t1, t2);
-                    r5 = make_float4(t0.x, t0.y, t0.z, 1.f / e.s.x);
-                    r6 = make_float4(t1.x, t1.y, t1.z, 1.f / e.s.y);
-                    r7 = make_float4(t2.x, t2.y, t2.z, 1.f / e.s.z);
-                }
-                const m3 rt = quat_wxyz_to_rotT(e.q.x, e.q.y, e.q.z, e.q.w);
-                const float ix = __builtin_amdgcn_rcpf(e.s.x), iy = __builtin_amdgcn_rcpf(e.s.y), iz = __builtin_amdgcn_rcpf(e.s.z);
-                r0 = make_float4(rt.r0.x * ix, rt.r0.y * ix, rt.r0.z * ix, e.a.x);
-                r1 = make_float4(rt.r1.x * iy, rt.r1.y * iy, rt.r1.z * iy, e.a.y);
-                r2 = make_float4(rt.r2.x * iz, rt.r2.y * iz, rt.r2.z * iz, e.a.z);
-                r3 = make_float4(e.s.x, e.s.y, e.s.z, e.a.w);
-                r4.x = __uint_as_float(e.idx);
-                // accept test on grayDist itself, as in the unsorted sweeps (stage_entry)
-                const float need = fmaxf(P.min_response, P.min_alpha / e.a.w);
-                r4.y = (P.max_alpha > P.min_alpha && e.a.w > 0.f) ? gray_limit_rt(P.degree, need) : 0.f;
-            }
-            float4* rec = &s_rec[lane * kQ];
-            rec[0] = r0; rec[1] = r1; rec[2] = r2; rec[3] = r3; rec[4] = r4; rec[5] = r5; rec[6] = r6; rec[7] = r7;
-        }
-        __syncthreads();
-        const int n = (int)min(64u, range.y - b);
-        for (int j = 0; j < n; ++j) {
-            if (!__any(alive)) break;
-            const float4* rec = &s_rec[j * kQ];
-            const uint32_t idx = __float_as_uint(rec[4].x);
-            if (idx == 0xFFFFFFFFu) break;   // padding closes the list (gutKBufferRenderer.cuh:312-315)
-            bool pop = false;
-            float pop_t = 0.f, pop_a = 0.f;
-            uint32_t pop_i = 0u;
-            if (alive) {
-                const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3];
-                const f3 dl = ray.o - mk3(q0.w, q1.w, q2.w);
-                const f3 gro = mk3(dot(mk3(q0.x, q0.y, q0.z), dl), dot(mk3(q1.x, q1.y, q1.z), dl), dot(mk3(q2.x, q2.y, q2.z), dl));
-                const f3 grdu = mk3(dot(mk3(q0.x, q0.y, q0.z), ray.d), dot(mk3(q1.x, q1.y, q1.z), ray.d), dot(mk3(q2.x, q2.y, q2.z), ray.d));
-                const float l2 = dot(grdu, grdu);
-                const f3 gc = cross(grdu, gro);
-                const float cc = dot(gc, gc);
-                if (cc < rec[4].y * l2) {   // response > min_response && alpha > min_alpha
-                    const float il2 = __builtin_amdgcn_rcpf(l2);
-                    const float resp = response_rt(P.degree, cc * il2);
-                    const float alpha = fminf(P.max_alpha, resp * q3.w);
-                    // hit distance |S n (n.-u)| (gaussianParticles.slang:181-190), bits = the checker's: it is the k-buffer's sort key
-                    const float4 q5 = rec[5], q6 = rec[6], q7 = rec[7];
-                    const float hitT = oracle_order_hit_t(ray, mk3(q0.w, q1.w, q2.w), mk3(q3.x, q3.y, q3.z), mk3(q5.x, q5.y, q5.z), mk3(q6.x, q6.y, q6.z),
-                                                          mk3(q7.x, q7.y, q7.z), mk3(q5.w, q6.w, q7.w));
-                    if ((hitT > ray.tmin) && (hitT < ray.tmax)) {
-                        if (kb.num == K) {   // full: the nearest pending hit is composited (below), the new one takes its slot
-                            pop = true; pop_t = kb.hitT[0]; pop_a = kb.alpha[0]; pop_i = kb.idx[0];
-                            kb.hitT[0] = -1.f;
-                        } else {
-                            kb.num++;
-                        }
-                        kb.insert(hitT, alpha, idx);
-                    }
-                }
-            }
-            if (BWD) {
-                if (__any(pop)) {   // wave-level: gradients of lanes that popped the same particle are summed before the atomics
-                    float terms[16];
-                    const bool have = pop && k_bwd_terms(P, ray, density12, rgb, pop_t, pop_a, pop_i, bs, alive, terms);
-                    if (kLdsFlush) k_bwd_flush_lds(have, pop_i, terms, lane, s_kterms, g_density12, g_rgb);
-                    else k_bwd_flush(have, pop_i, terms, lane, g_density12, g_rgb);
-                }
-            } else if (pop) {
-                k_process_fwd(P, rgb, pop_t, pop_a, pop_i, fs, alive);
-            }
-        }
-        __syncthreads();
-    }
-    // drain what is left, nearest first (:343-351).  The buffer is ascending with the empty slots (hitT = -1) in front: K steps
-    // that each take slot 0 and shift the rest down visit the pending hits in order; one copy of the per-hit code instead of K
-    // (the gradient terms alone are ~600 instructions).
-#pragma unroll 1
-    for (int step = 0; step < K; ++step) {
-        const float t0 = kb.hitT[0], a0 = kb.alpha[0];
-        const uint32_t i0 = kb.idx[0];
-#pragma unroll
-        for (int i = 0; i + 1 < K; ++i) { kb.hitT[i] = kb.hitT[i + 1]; kb.alpha[i] = kb.alpha[i + 1]; kb.idx[i] = kb.idx[i + 1]; }
-        kb.hitT[K - 1] = -1.f;
-        const bool act = alive && (t0 >= 0.f);
-        if (BWD) {
-            if (__any(act)) {
-                float terms[16];
-                const bool have = act && k_bwd_terms(P, ray, density12, rgb, t0, a0, i0, bs, alive, terms);
-                if (kLdsFlush) k_bwd_flush_lds(have, i0, terms, lane, s_kterms, g_density12, g_rgb);
-                else k_bwd_flush(have, i0, terms, lane, g_density12, g_rgb);
-            }
-        } else if (act) {
-            k_process_fwd(P, rgb, t0, a0, i0, fs, alive);
-        }
-    }
-    if (!BWD && ray.inside) {
-        const size_t opix = (size_t)py * P.W + px;
-        const float4 o = ray.valid ? make_float4(fs.Cr, fs.Cg, fs.Cb, 1.f - fs.T) : make_float4(0.f, 0.f, 0.f, 0.f);
-        store_fd(P, out_fd, opix, o);
-        write_split_outputs(P, opix, o);
-        out_dist[opix] = ray.valid ? fs.D : 1e6f;
-        if (P.hitcounts) out_cnt[opix] = ray.valid ? fs.cnt : 0.f;
-    }
-}
-
-// The forward fits three waves per SIMD when told to (1.96 vs 2.5 ms at K = 16); the backward needs its 231 registers
-// (8.0 ms at two waves, 9.6 at three, 13.3 at four).
-#ifndef GRUT_K_FWD_WAVES
-#define GRUT_K_FWD_WAVES 3   // (measured again in round 5 with the exact-order hit distance: forward 3.07 / 2.61 / 3.08 ms at 2 / 3 / 4 waves)
-#endif
-template <int K>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GRUT_K_FWD_WAVES))) void gut_render_k_fwd_kernel(
-    GutParams P, const uint2* __restrict__ ranges, EntryLists lists, const float4* __restrict__ density12, const float* __restrict__ rgb,
-    const float* __restrict__ ray_o, const float* __restrict__ ray_d, float4* __restrict__ out_fd, float* __restrict__ out_dist,
-    float* __restrict__ out_cnt) {
-    gut_render_k_body<K, false>(P, ranges, lists, density12, rgb, ray_o, ray_d, out_fd, out_dist, out_cnt, nullptr, nullptr, nullptr, nullptr);
-}
-// K = 16 with the LDS flush: 209 VGPRs where the DPP reduce-scatter needed 231 - held to 168 (116 B of scratch) the kernel runs three waves
-// per SIMD: backward 8.59 -> 7.60 ms (A/B on one box; the LDS flush at two waves: 8.98, the DPP flush at three: 9.6 in round 2).  K = 8: 177 ->
-// 161 VGPRs, three waves without scratch, backward 6.53 -> 6.06 ms.
-#ifndef GRUT_K_BWD_WAVES
-#define GRUT_K_BWD_WAVES 3
-#endif
-template <int K>
-__global__ __launch_bounds__(64)
-__attribute__((amdgpu_waves_per_eu((K >= GRUT_K_FLUSH_MINK && GRUT_K_FLUSH_LDS) ? GRUT_K_BWD_WAVES : 1, (K >= GRUT_K_FLUSH_MINK && GRUT_K_FLUSH_LDS) ? GRUT_K_BWD_WAVES : 8)))
-void gut_render_k_bwd_kernel(GutParams P, const uint2* __restrict__ ranges, EntryLists lists,
-                                                              const float4* __restrict__ density12, const float* __restrict__ rgb,
-                                                              const float* __restrict__ ray_o, const float* __restrict__ ray_d,
-                                                              float4* __restrict__ fd, float* __restrict__ dist, const float4* __restrict__ g_fd,
-                                                              const float* __restrict__ g_dist, float* __restrict__ g_density12,
-                                                              float* __restrict__ g_rgb) {
-    gut_render_k_body<K, true>(P, ranges, lists, density12, rgb, ray_o, ray_d, fd, dist, nullptr, g_fd, g_dist, g_density12, g_rgb);
-}
-
 }  // namespace
 
-// ---------------------------------------------------------------------------------------------
-// launchers
-// ---------------------------------------------------------------------------------------------
-static uint32_t half_grid(const GutParams& P) {
-    const uint32_t tiles = (uint32_t)(P.gx * P.gy);
-    return ((tiles + 7u) & ~7u) * 2u;
-}
-// tile-first segments + one task set per segment boundary, padded to the 8-XCD interleave
-static uint32_t segment_grid(const GutParams& P, uint32_t num_boundaries) {
-    const uint32_t tiles = (uint32_t)(P.gx * P.gy);
-    const uint32_t vtiles = ((tiles + 7u) & ~7u) + ((num_boundaries + 7u) & ~7u);
-    return vtiles * 2u;
-}
-
-#define GRUT_DISPATCH_DEGREE(DEG, ...)                         \
-    switch (DEG) {                                             \
-    case 0: { constexpr int D_ = 0; __VA_ARGS__; } break;      \
-    case 1: { constexpr int D_ = 1; __VA_ARGS__; } break;      \
-    case 3: { constexpr int D_ = 3; __VA_ARGS__; } break;      \
-    case 4: { constexpr int D_ = 4; __VA_ARGS__; } break;      \
-    case 5: { constexpr int D_ = 5; __VA_ARGS__; } break;      \
-    case 8: { constexpr int D_ = 8; __VA_ARGS__; } break;      \
-    default: { constexpr int D_ = 2; __VA_ARGS__; } break;     \
-    }
-
-#if GRUT_RENDER_PART != 1   // everything but the sorted hit buffer with SH radiance
 void launch_render_fwd(hipStream_t s, const GutParams& P, const uint32_t* ranges, const uint32_t* sorted_pos, const uint32_t* pos_particle,
                        const float* density12, const float* rgb, const float* ray_o, const float* ray_d, float* out_fd, float* out_dist,
                        float* out_cnt, const GutCheckpoints& ck, bool write_checkpoints) {
@@ -2535,18 +1550,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FAST ? GRUT_
 
 #include "gut_render_nht.inl"
 
-#endif   // GRUT_RENDER_PART != 1
-static uint32_t strip_grid(const GutParams& P) {
-    const uint32_t tiles = (uint32_t)(P.gx * P.gy);
-    return ((tiles + 7u) & ~7u) * 4u;
-}
-#define GRUT_DISPATCH_K(KK, ...)                               \
-    switch (KK) {                                              \
-    case 4: { constexpr int K_ = 4; __VA_ARGS__; } break;      \
-    case 8: { constexpr int K_ = 8; __VA_ARGS__; } break;      \
-    default: { constexpr int K_ = 16; __VA_ARGS__; } break;    \
-    }
-#if GRUT_RENDER_PART != 1
 bool nht_fast_path(const GutParams& P) {
     const bool generic = getenv("GRUT_NHT_GENERIC") != nullptr;   // (development / test switch, read per call: the strip kernels for every shape)
     return P.nht && !generic && P.nht_k == kNhtK && P.nht_ipd == kNhtIpd && P.nht_support == 1 && P.nht_act == 2 && P.nht_nf == 1 && P.k_buffer == 0;
@@ -2629,25 +1632,5 @@ void launch_render_nht_bwd(hipStream_t s, const GutParams& P, const uint32_t* ra
     hipLaunchKernelGGL(gut_render_nht_bwd_kernel, dim3(strip_grid(P)), dim3(64), 0, s, P, reinterpret_cast<const uint2*>(ranges), lists,
                        reinterpret_cast<const float4*>(density12), features, ray_o, ray_d, fd, g_fd, dist, g_dist, g_density12, g_features);
 }
-#endif   // GRUT_RENDER_PART != 1
-#if GRUT_RENDER_PART != 0   // the sorted hit buffer's launchers (and, through them, its kernels' instantiations): see the note at the top
-void launch_render_k_fwd(hipStream_t s, const GutParams& P, const uint32_t* ranges, const uint32_t* sorted_pos, const uint32_t* pos_particle,
-                         const float* density12, const float* rgb, const float* ray_o, const float* ray_d, float* out_fd, float* out_dist,
-                         float* out_cnt) {
-    const EntryLists lists = entry_lists(P, sorted_pos, pos_particle);
-    GRUT_DISPATCH_K(P.k_buffer, hipLaunchKernelGGL((gut_render_k_fwd_kernel<K_>), dim3(strip_grid(P)), dim3(64), 0, s, P,
-                                                   reinterpret_cast<const uint2*>(ranges), lists, reinterpret_cast<const float4*>(density12), rgb,
-                                                   ray_o, ray_d, reinterpret_cast<float4*>(out_fd), out_dist, out_cnt));
-}
-void launch_render_k_bwd(hipStream_t s, const GutParams& P, const uint32_t* ranges, const uint32_t* sorted_pos, const uint32_t* pos_particle,
-                         const float* density12, const float* rgb, const float* ray_o, const float* ray_d, const float* fd, const float* g_fd,
-                         const float* dist, const float* g_dist, float* g_density12, float* g_rgb) {
-    const EntryLists lists = entry_lists(P, sorted_pos, pos_particle);
-    GRUT_DISPATCH_K(P.k_buffer, hipLaunchKernelGGL((gut_render_k_bwd_kernel<K_>), dim3(strip_grid(P)), dim3(64), 0, s, P,
-                                                   reinterpret_cast<const uint2*>(ranges), lists, reinterpret_cast<const float4*>(density12), rgb,
-                                                   ray_o, ray_d, reinterpret_cast<float4*>(const_cast<float*>(fd)), const_cast<float*>(dist),
-                                                   reinterpret_cast<const float4*>(g_fd), g_dist, g_density12, g_rgb));
-}
 
-#endif   // GRUT_RENDER_PART != 0
 }  // namespace grut

@@ -54,7 +54,7 @@ def test_gut_non_default_configurations_meet_the_staged_method_at_baseline_size(
     stats = pu.gut_full_parity(N, W, H, 0.01, log=print, device_pose=True, end_to_end=False, variant=VARIANTS[variant])
     # sorted mode: the k-buffer orders hits by their fp32 hit distance.  Until round 4 the kernels and the checker evaluated that distance
     # in different operation orders, pairs of hits that tie to rounding popped in either order and 0.34 % of the frame needed an exemption
-    # of its own.  Now the kernels evaluate it in the checker's order (csrc/gut_render.hip: oracle_order_hit_t): same bits, same order, the
+    # of its own.  Now the kernels evaluate it in the checker's order (csrc/gut_render_common.inl: oracle_order_hit_t): same bits, same order, the
     # DEFAULT limits (measured round 5: 0.055 % exempt, every pixel identified, no order swap among the toggles) - and nothing beyond 1e-2
     # outside the identified accept / termination flips.
     pu.record_full_parity(f"c4_1m_1080p_{variant}", stats)

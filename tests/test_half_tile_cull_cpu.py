@@ -1,4 +1,4 @@
-"""The half-tile culling of the 3DGUT forward (3dgrut_amd/csrc/gut_render.hip: WavePyramid, pyramid_misses),
+"""The half-tile culling of the 3DGUT forward (3dgrut_amd/csrc/gut_render_common.inl: WavePyramid, pyramid_misses),
 checked as mathematics in float64 against brute force.  The kernel drops a staged entry when, in the particle's canonical frame, the sphere of
 radius r = sqrt(gmax) around the origin lies wholly in front of the image of the camera plane AND wholly outside one face of the pyramid
 that bounds the wave's rays.  The accept test it must never pre-empt is the LINE - sphere test  |v x u|^2 < gmax |v|^2  (u = M (o - mu),
