@@ -169,6 +169,7 @@ EXPORTED_SYMBOLS = [
     "grut_knn", "grut_knn_scratch_bytes",
     "grut_ppisp_forward", "grut_ppisp_backward", "grut_ppisp_partials",
     "grut_mlp_forward", "grut_mlp_lds_bytes", "grut_mlp_num_params",
+    "grut_mlp_backward", "grut_mlp_backward_lds_bytes", "grut_mlp_backward_scratch_bytes",
     "grut_last_error", "grut_abi_version", "grut_set_allocator", "gut_trim", "grt_trim",
 ]
 
@@ -329,6 +330,13 @@ def _declare(lib):
     lib.grut_mlp_lds_bytes.restype = C.c_uint32
     lib.grut_mlp_num_params.argtypes = [C.POINTER(GrutMlpConfig)]
     lib.grut_mlp_num_params.restype = C.c_uint32
+    # stream, config, params, input [P, F + 3], grad_out [P, n_output_dims], num_pixels, scratch, grad_input or NULL, grad_params or NULL
+    lib.grut_mlp_backward.argtypes = [vp, C.POINTER(GrutMlpConfig), fp, fp, fp, C.c_uint32, vp, fp, fp]
+    lib.grut_mlp_backward.restype = C.c_int
+    lib.grut_mlp_backward_lds_bytes.argtypes = [C.POINTER(GrutMlpConfig)]
+    lib.grut_mlp_backward_lds_bytes.restype = C.c_uint32
+    lib.grut_mlp_backward_scratch_bytes.argtypes = [C.POINTER(GrutMlpConfig), C.c_uint32]
+    lib.grut_mlp_backward_scratch_bytes.restype = C.c_size_t
     lib.grut_last_error.argtypes = []
     lib.grut_last_error.restype = C.c_char_p
     lib.grut_abi_version.argtypes = []

@@ -115,4 +115,63 @@ GRUT_MLP_HD uint32_t lds_bytes(const Shape& s) {
     return b <= kLdsLimit ? b : 0;
 }
 
+// ---- the backward (mlp_backward.hip) -----------------------------------------------------------------------------------------------------
+// One workgroup of kBwdWaves waves takes kBwdPixels pixels per step, wave w the 32 pixels 32 w .. 32 w + 31.  Gradients keep the
+// forward's orientation, [neuron rows x 32 pixel columns]: dZ of a layer in the C / D layout IS the B operand of dH = W^T dZ (k-step
+// 2 b + s = registers 8 s .. 8 s + 7 of row block b, the k order of mlp_kperm), and the A operand W^T comes out of the forward's image
+// through ds_read_b64_tr_b16 (bwd_wt_read_offset).  The weight gradient dW = dZ H^T sums over the pixel, the lane of both operands, so
+// both cross LDS once: the workgroup stages its 128 pixels of dZ and H as [pixel][neuron] bf16 tiles (bwd_stage_*), and wave w owns the
+// 32 x 32 tiles w, w + 4, .. of every layer's dW (bwd_dw_*), accumulated in registers over all steps of the workgroup.
+//
+// ds_read_b64_tr_b16, per group of 16 consecutive lanes: lane 4 q + p supplies the address of 4 consecutive 16-bit elements, row q of a
+// 4 x 16 block at columns 4 p .. 4 p + 3; lane i receives column i, row q in its element q.
+constexpr int kBwdWaves = 4, kBwdPixels = kBwdWaves * kTile;
+constexpr int kBwdMaxGrid = 256;      // workgroups at most, whatever the device: the scratch is bounded by kBwdMaxGrid partials of grad_params
+
+// 32-column blocks of a layer's input (K0 rounded up: the columns beyond K0 are computed and dropped)
+GRUT_MLP_HD int bwd_kblocks(const Shape& s, int layer) { return (layer_in(s, layer) + kTile - 1) / kTile; }
+// 32-column subtiles of a staged tile: wide enough for a hidden activation and for the encoded input
+GRUT_MLP_HD int bwd_stage_subtiles(const Shape& s) { return row_blocks(s) > bwd_kblocks(s, 0) ? row_blocks(s) : bwd_kblocks(s, 0); }
+GRUT_MLP_HD uint32_t bwd_stage_bytes(const Shape& s) { return (uint32_t)(kBwdPixels * bwd_stage_subtiles(s) * kTile * 2); }
+// A staged tile [kBwdPixels pixel rows][32-column subtiles] of bf16: every subtile is a contiguous [128 pixels][32 neurons] block of 8 KiB
+// with 64-byte rows whose 16-byte chunks are XOR-swizzled by the row (the conflict-free image of 8-row x 32-column subtiles, stacked):
+// byte offset of chunk ch (8 neurons) of pixel row `row`.  No offset depends on the tile's width.
+GRUT_MLP_HD uint32_t bwd_stage_offset(int row, int ch) {
+    return (uint32_t)(kBwdPixels * 64 * (ch >> 2) + 64 * row + 16 * ((ch & 3) ^ ((row >> 2) & 3)));
+}
+// where lane half h of the wave's pixel row stores the 8 bytes of elements 4 c .. 4 c + 3 of a packed fragment of k-step t
+// (neurons 16 t + 8 c + 4 h .. + 3)
+GRUT_MLP_HD uint32_t bwd_stage_store_offset(int pixel, int t, int c, int h) { return bwd_stage_offset(pixel, 2 * t + c) + 8u * (uint32_t)h; }
+// the address lane `lane` supplies to transposed read c (0, 1) of the fragment (32-neuron block blk, pixel k-step kk) of a staged tile:
+// the lane then holds neuron 32 blk + (lane & 31), pixels 16 kk + 8 h + 4 c + q in element 4 c + q, as A or as B operand
+GRUT_MLP_HD uint32_t bwd_stage_read_offset(int blk, int kk, int c, int lane) {
+    const int h = lane >> 5, g = (lane >> 4) & 1, q = (lane & 15) >> 2, p = lane & 3;
+    return bwd_stage_offset(kStep * kk + 8 * h + 4 * c + q, 4 * blk + 2 * g + (p >> 1)) + 8u * (uint32_t)(p & 1);
+}
+// the address lane `lane` supplies to transposed read c (0, 1) of the W^T fragment (k block kb of the layer's input, k-step tp of its
+// output rows) in the FORWARD's image: the lane then holds W[row 16 tp + 8 c + 4 h + q][k = 32 kb + (lane & 31)] in element 4 c + q, the
+// order of mlp_kperm.  A k-step beyond the layer's last (K0 not a multiple of 32) is clamped: those rows of dH are dropped.
+GRUT_MLP_HD uint32_t bwd_wt_read_offset(const Shape& s, int layer, int kb, int tp, int c, int lane) {
+    const int h = lane >> 5, g = (lane >> 4) & 1, q = (lane & 15) >> 2, p = lane & 3;
+    const int row = kStep * tp + 8 * c + 4 * h + q, nk = layer_ksteps(s, layer);
+    const int t = 2 * kb + g < nk ? 2 * kb + g : nk - 1;
+    return image_offset(s, layer, row >> 5, t, 32 * (p & 1) + (row & 31)) + 8u * (uint32_t)(p >> 1);
+}
+// dW of a layer in 32 x 32 tiles, tile i = (row block i / kblocks, k block i % kblocks); wave w owns tiles w, w + kBwdWaves, ..
+GRUT_MLP_HD int bwd_dw_tiles(const Shape& s, int layer) { return layer_row_blocks(s, layer) * bwd_kblocks(s, layer); }
+GRUT_MLP_HD int bwd_dw_slots(const Shape& s, int layer) { return (bwd_dw_tiles(s, layer) + kBwdWaves - 1) / kBwdWaves; }
+GRUT_MLP_HD int bwd_dw_tile(int slot, int wave) { return slot * kBwdWaves + wave; }
+
+// LDS of the backward: the forward's image, then the staged dZ tile, then the staged H tile; 0 when it does not fit
+GRUT_MLP_HD uint32_t bwd_lds_bytes(const Shape& s) {
+    if (!lds_bytes(s)) return 0;
+    const uint32_t b = image_bytes(s) + 2u * bwd_stage_bytes(s);
+    return b <= kLdsLimit ? b : 0;
+}
+GRUT_MLP_HD uint32_t bwd_steps(uint32_t P) { return (uint32_t)(((uint64_t)P + kBwdPixels - 1) / kBwdPixels); }
+GRUT_MLP_HD uint32_t bwd_grid(uint32_t P, uint32_t cus) {
+    const uint32_t cap = cus < (uint32_t)kBwdMaxGrid ? (cus ? cus : 1u) : (uint32_t)kBwdMaxGrid, steps = bwd_steps(P);
+    return steps < cap ? steps : cap;
+}
+
 }  // namespace grut_mlp

@@ -1,11 +1,14 @@
 """The NHT decoder's network on the MI355X: drop-in for the CUDA-only package `tinycudann` that the reference's feature decoder imports
-(threedgrut/model/feature_decoder.py:16) for `model.feature_type: nht`, with a fused HIP forward (csrc/mlp.hip).
+(threedgrut/model/feature_decoder.py:16) for `model.feature_type: nht`, with a fused HIP forward (csrc/mlp.hip) and an opt-in fused HIP
+backward (csrc/mlp_backward.hip).
 
     NetworkWithInputEncoding(n_input_dims=F+3, n_output_dims=, encoding_config=, network_config=, seed=1337)
                 the module the decoder builds (feature_decoder.py:69-99): `params` (one flat fp32 nn.Parameter), n_input_dims,
                 n_output_dims, n_params; called with [P, F+3] rows whose last three columns are (dir * sh_scale + 1) / 2 -> [P, n_output_dims] fp32
     mlp_torch(params, x, cfg)   the same model in plain torch, on any device and float dtype, differentiable in x and params: the path of
                 everything the kernel does not take, the backward of the training step, and the benchmark's baseline (scripts/bench_mlp.py)
+    mlp_backward_torch(params, x, grad_out, cfg)   the contract of grut_mlp_backward in plain torch, on any device -> (grad_x, grad_params)
+    install_fused_backward(enable=True)   opt-in: the training step's backward runs csrc/mlp_backward.hip; returns the previous state
     install()   registers a module named `tinycudann` (unless one is already in sys.modules); called by the tracer shims
 
 The model - encoding, layer shapes, the layout of `params`, the bf16 rounding points - is stated at grut_mlp_forward in include/grut_amd.h.
@@ -14,9 +17,13 @@ tiny-cuda-nn's source is not part of the reference checkout, so everything beyon
 
 Dispatch.  A contiguous fp32 CUDA [P >= 1, F+3] input with fp32 `params` on the same device, width 64 or 128, n_output_dims <= 16,
 K0 <= 128 and a weight image that fits into LDS runs the HIP kernel; anything else runs mlp_torch, which agrees with it within the
-tolerance of tests/mlp_reference.py.  With grad enabled the forward is still the kernel; the backward re-runs mlp_torch on the saved
-input and weights (the fused backward is a follow-up).  The kernel reads `params` afresh at every launch: nothing derived from the
-weights is kept anywhere, because the decoder's EMA swaps them through `param.data.copy_`, which no version counter sees.
+tolerance of tests/mlp_reference.py.  With grad enabled the forward is still the kernel.  The backward, by default, re-runs mlp_torch
+on the saved input and weights under autograd.  After install_fused_backward() it is ONE fused HIP kernel (plus an ordered reduction of
+the weight gradient) for every configuration with grut_mlp_backward_lds_bytes != 0: it recomputes the forward from the saved input and
+the live weights, rounds every dZ once to bf16 and sums in fp32 without atomics (the rules: grut_mlp_backward in include/grut_amd.h;
+mlp_backward_torch states them in torch).  The switch is off by default until a training run of an NHT configuration has used it.
+Both kernels read `params` afresh at every launch: nothing derived from the weights is kept anywhere, because the decoder's EMA swaps
+them through `param.data.copy_`, which no version counter sees.
 """
 from __future__ import annotations
 
@@ -35,7 +42,8 @@ from . import _abi
 SHIM_MODULE = "tinycudann"
 OUT_ROWS = 16                 # rows of the output matrix in `params`
 ACTIVATIONS = {"none": _abi.MLP_ACT_NONE, "relu": _abi.MLP_ACT_RELU, "sigmoid": _abi.MLP_ACT_SIGMOID}
-stats = {"hip_calls": 0, "torch_calls": 0, "backward_calls": 0}   # which path ran (tests); plain counters
+stats = {"hip_calls": 0, "torch_calls": 0, "backward_calls": 0, "hip_backward_calls": 0}   # which path ran (tests); plain counters
+_fused_backward = False       # install_fused_backward()
 
 
 class MlpConfig(NamedTuple):
@@ -112,6 +120,67 @@ def mlp_torch(params, x, cfg: MlpConfig):
     return h
 
 
+def sh_jacobian(d, degree: int):
+    """d sh_encoding(d, degree) / d d for d [P, 3] -> [P, degree^2, 3]"""
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    xx, yy, zz = x * x, y * y, z * z
+    o, one = torch.zeros_like(x), torch.ones_like(x)
+    c1, c2, c3, c5 = 0.48860251190291987, 1.0925484305920792, 0.94617469575755997, 0.54627421529603959
+    c6, c7, c8, c9, c10 = 0.59004358992664352, 2.8906114426405538, 0.45704579946446572, 0.3731763325901154, 1.4453057213202769
+    rows = [(o, o, o), (o, -c1 * one, o), (o, o, c1 * one), (-c1 * one, o, o), (c2 * y, c2 * x, o), (o, -c2 * z, -c2 * y), (o, o, 2 * c3 * z),
+            (-c2 * z, o, -c2 * x), (2 * c5 * x, -2 * c5 * y, o), (-6 * c6 * x * y, c6 * (-3 * xx + 3 * yy), o),
+            (c7 * y * z, c7 * x * z, c7 * x * y), (o, c8 * (1 - 5 * zz), -10 * c8 * y * z), (o, o, c9 * (15 * zz - 3)),
+            (c8 * (1 - 5 * zz), o, -10 * c8 * x * z), (2 * c10 * x * z, -2 * c10 * y * z, c10 * (xx - yy)),
+            (c6 * (-3 * xx + 3 * yy), 6 * c6 * x * y, o)]
+    return torch.stack([torch.stack(r, dim=-1) for r in rows[:degree * degree]], dim=-2)
+
+
+@torch.no_grad()
+def mlp_backward_torch(params, x, grad_out, cfg: MlpConfig):
+    """The contract of grut_mlp_backward (include/grut_amd.h) in plain torch, on any device: fp64 arithmetic for an fp64 x, fp32
+    otherwise.  The forward is computed again with its rounding points; every dZ (the gradient with respect to a layer's pre-activation,
+    after its ReLU gate or the output activation's derivative) is rounded once to bf16 and that rounded dZ enters both W^T dZ and
+    dZ H^T; the forward's roundings are straight-through; the SH Jacobian and the factor 2 are not rounded.
+    -> (grad_x [P, F+3], grad_params [n_params]) in that dtype; the output matrix's rows >= n_output_dims get zero."""
+    dt = torch.float64 if x.dtype == torch.float64 else torch.float32
+
+    def rb(t):
+        return t.to(torch.bfloat16).to(dt)
+
+    x = x.to(dt)
+    f, k0, n_sh = cfg.n_features, cfg.k0, cfg.sh_degree ** 2
+    d = 2.0 * x[:, f:f + 3] - 1.0
+    enc = [x[:, :f], sh_encoding(d, cfg.sh_degree)]
+    if k0 > f + n_sh:
+        enc.append(torch.ones((x.shape[0], k0 - f - n_sh), dtype=dt, device=x.device))
+    hs, zs, ws, offset = [rb(torch.cat(enc, dim=1))], [], [], 0
+    for i, (rows, columns) in enumerate(cfg.matrices):
+        used = cfg.n_output_dims if i == cfg.n_hidden_layers else rows
+        ws.append(rb(params[offset:offset + used * columns].to(dt).reshape(used, columns)))
+        offset += rows * columns
+        zs.append(hs[-1] @ ws[-1].T)
+        if i < cfg.n_hidden_layers:
+            hs.append(rb(torch.relu(zs[-1])))
+    g = grad_out.to(dt)
+    if cfg.output_activation == "relu":
+        g = g * (zs[-1] > 0)
+    elif cfg.output_activation == "sigmoid":
+        y = torch.sigmoid(zs[-1])
+        g = g * (y * (1.0 - y))
+    grads = []
+    for i in range(cfg.n_hidden_layers, -1, -1):
+        if i < cfg.n_hidden_layers:
+            g = g * (zs[i] > 0)
+        g = rb(g)
+        gw = g.T @ hs[i]
+        if i == cfg.n_hidden_layers:
+            gw = torch.cat([gw, torch.zeros((OUT_ROWS - cfg.n_output_dims, gw.shape[1]), dtype=dt, device=x.device)])
+        grads.insert(0, gw.reshape(-1))
+        g = g @ ws[i]
+    g_d = torch.einsum("pi,pic->pc", g[:, f:f + n_sh], sh_jacobian(d, cfg.sh_degree))
+    return torch.cat([g[:, :f], 2.0 * g_d], dim=1), torch.cat(grads)
+
+
 # ---- the HIP path -----------------------------------------------------------------------------------------------------------------------------
 def lds_bytes(cfg: MlpConfig) -> int:
     """grut_mlp_lds_bytes: the size of the kernel's weight image, 0 when the kernel does not take the configuration"""
@@ -139,8 +208,45 @@ def mlp_forward_hip(params, x, cfg: MlpConfig):
     return out
 
 
+def backward_lds_bytes(cfg: MlpConfig) -> int:
+    """grut_mlp_backward_lds_bytes: the LDS of the fused backward, 0 when it does not take the configuration"""
+    if cfg.output_activation not in ACTIVATIONS:
+        return 0
+    return int(_abi.load_library().grut_mlp_backward_lds_bytes(C.byref(cfg.as_struct())))
+
+
+def mlp_backward_hip(params, x, grad_out, cfg: MlpConfig, need_x: bool = True, need_params: bool = True):
+    """csrc/mlp_backward.hip on tensors that takes_hip() accepts, for a configuration with backward_lds_bytes != 0 and a contiguous fp32
+    grad_out [P, n_output_dims] -> (grad_x or None, grad_params or None).  The scratch comes from torch's allocator, per call."""
+    lib = _abi.load_library()
+    struct, n = cfg.as_struct(), x.shape[0]
+    grad_x = torch.empty_like(x) if need_x else None
+    grad_params = torch.empty_like(params) if need_params else None
+    scratch = None
+    if need_params:
+        scratch = torch.empty(int(lib.grut_mlp_backward_scratch_bytes(C.byref(struct), n)), dtype=torch.uint8, device=x.device)
+    stats["hip_backward_calls"] += 1
+    with torch.cuda.device(x.device):
+        _abi.check(lib.grut_mlp_backward(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), C.byref(struct),
+                                         C.c_void_p(params.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(grad_out.data_ptr()), n,
+                                         C.c_void_p(scratch.data_ptr() if need_params else None),
+                                         C.c_void_p(grad_x.data_ptr() if need_x else None),
+                                         C.c_void_p(grad_params.data_ptr() if need_params else None)),
+                   "grut_mlp_backward")
+    return grad_x, grad_params
+
+
+def install_fused_backward(enable: bool = True) -> bool:
+    """Opt-in: while on, the backward of the training Function runs the fused HIP kernel wherever it takes the tensors and the
+    configuration (takes_hip, backward_lds_bytes != 0); everything else keeps the mlp_torch backward.  Returns the previous state."""
+    global _fused_backward
+    previous, _fused_backward = _fused_backward, bool(enable)
+    return previous
+
+
 class _MlpFunction(torch.autograd.Function):
-    """The training step: the forward is the kernel and keeps only x and params; the backward recomputes mlp_torch from them."""
+    """The training step: the forward is the kernel and keeps only x and params; the backward recomputes the forward from them, in
+    mlp_torch under autograd or, after install_fused_backward(), in the fused kernel."""
 
     @staticmethod
     def forward(ctx, x, params, cfg):
@@ -154,6 +260,11 @@ class _MlpFunction(torch.autograd.Function):
         x, params = ctx.saved_tensors
         need_x, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         stats["backward_calls"] += 1
+        if _fused_backward and (need_x or need_p) and takes_hip(params, x, ctx.cfg) and backward_lds_bytes(ctx.cfg) != 0 \
+                and grad_out.device == x.device:
+            grad_x, grad_params = mlp_backward_hip(params.detach(), x.detach(), grad_out.detach().to(torch.float32).contiguous(), ctx.cfg,
+                                                   need_x, need_p)
+            return grad_x, grad_params, None
         with torch.enable_grad():
             xg, pg = x.detach().requires_grad_(need_x), params.detach().requires_grad_(need_p)
             y = mlp_torch(pg, xg, ctx.cfg)

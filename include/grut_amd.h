@@ -718,6 +718,38 @@ uint32_t grut_mlp_num_params(const GrutMlpConfig* config);
 uint32_t grut_mlp_lds_bytes(const GrutMlpConfig* config);
 int grut_mlp_forward(void* stream, const GrutMlpConfig* config, const float* params, const float* input, uint32_t num_pixels, float* out);
 
+/* The backward of grut_mlp_forward, fused: from the saved input rows, the LIVE `params` and grad_out [P, n_output_dims] to
+ * grad_input [P, F + 3] and grad_params [grut_mlp_num_params]; either may be NULL (then it is not computed), both NULL is
+ * GRUT_ERR_BAD_INPUT.  This project's rules:
+ *   recomputation  the forward is computed again from input and params with the forward's rounding points (bf16 nearest even for the
+ *           weights, the encoded input and the post-ReLU hidden activations; fp32 sums).  No forward intermediate is kept between the two
+ *           calls, and `params` is read afresh at every launch: nothing derived from the weights is cached anywhere.
+ *   gates   a hidden ReLU passes gradient where its recomputed pre-activation is > 0 (read off the rounded activation: non-zero; the two
+ *           differ only for a pre-activation below bf16's smallest subnormal).  The output activation's derivative is fp32 from the
+ *           recomputed output: y (1 - y) for sigmoid, z > 0 for ReLU, 1 for none.
+ *   dZ      the gradient with respect to a layer's pre-activation, after its gate or activation derivative, is rounded ONCE to bf16
+ *           (nearest even) before it enters any product; the data gradient W^T dZ and the weight gradient dZ H^T use that same rounded dZ,
+ *           and H is the very rounded operand of the recomputed forward.
+ *   sums    every sum is fp32; the SH Jacobian, the factor 2 of d = 2 u - 1 and grad_input are fp32; the forward's bf16 roundings are
+ *           straight-through.
+ *   outputs grad_params is written completely: rows >= n_output_dims of the output matrix get +0.0, the ones-padded columns of the first
+ *           matrix their real gradient (they are the learnable bias).  Nothing has to be zeroed by the caller.
+ *   order   no atomics.  Every workgroup sums its pixels (steps of 128, workgroup b takes steps b, b + grid, ..) in registers and writes one
+ *           partial of grad_params to `scratch`; a second kernel sums the partials in workgroup order.  The grid is
+ *           min(ceil(P / 128), compute units, 256), so the order depends on (config, P, device) only: two calls are bitwise equal, and
+ *           grad_input does not depend on whether grad_params is asked for.
+ *   memory  `scratch` (needed only with grad_params): grut_mlp_backward_scratch_bytes(config, P) = min(ceil(P / 128), 256) partials of
+ *           grut_mlp_num_params floats, whatever the device; bounded independently of P, no per-pixel data.  No allocation and no
+ *           synchronisation inside the call; two launches on `stream`.
+ * grut_mlp_backward_lds_bytes: the kernel's LDS (the forward's image plus two staged tiles of 128 pixels x max(width, K0 rounded up to 32)
+ * bf16), or 0 for a configuration the backward does not take: one the forward does not take, more than 5 hidden layers, or an image that
+ * leaves no room for the tiles within 160 KiB (3 layers of 128 with K0 > 96; 5 layers of 128).  grut_mlp_backward on such a configuration,
+ * with unaligned `params` or with num_pixels == 0 is GRUT_ERR_BAD_INPUT before anything is launched. */
+uint32_t grut_mlp_backward_lds_bytes(const GrutMlpConfig* config);
+size_t grut_mlp_backward_scratch_bytes(const GrutMlpConfig* config, uint32_t num_pixels);
+int grut_mlp_backward(void* stream, const GrutMlpConfig* config, const float* params, const float* input, const float* grad_out,
+                      uint32_t num_pixels, void* scratch, float* grad_input, float* grad_params);
+
 /* ---- nearest-neighbour initialisation (threedgrut/model/geometry.py) ----------------------------------------------- */
 /* Exact k nearest neighbours in 3-D, the device side of what the reference's initialisation takes from sklearn.neighbors:
  * k_nearest_neighbors (geometry.py:42-49, called at model.py:732 for the Gaussians' initial size), nearest_neighbors (geometry.py:52-73)

@@ -1,5 +1,5 @@
 """The NHT decoder's network (3dgrut_amd/tcnn.py) at the shipped shape - 24 features, SH degree 3, 3 hidden layers of 128, sigmoid -
-four ways on one MI355X, in one process, alternating:
+five ways on one MI355X, in one process, alternating:
 
     python scripts/bench_mlp.py [--rounds 15] [--window 0.2] [--size 1080p|800x800|all] [--time-limit 300] [--out profiles/mlp_bench.json]
 
@@ -7,6 +7,7 @@ four ways on one MI355X, in one process, alternating:
   fused_fwd        the fused HIP forward (csrc/mlp.hip), under no_grad: inference, validation, the GUI
   fused_fwd_bwd    the training Function: the HIP forward, then a backward that recomputes mlp_torch from the saved input and weights
   torch_fwd_bwd    mlp_torch alone, forward and autograd's backward
+  fused_step       the training Function after install_fused_backward(): the HIP forward and the fused HIP backward (csrc/mlp_backward.hip)
 
 Random data: weights from the module's Xavier initialisation, features ~ N(0, 0.5), unit directions scaled by sh_scale = 3 (zero-filled
 operands would read high).  The fused forward is first held against mlp_torch on the timed input.  Method of scripts/bench_ppisp.py:
@@ -87,7 +88,21 @@ def main():
             params.grad = xg.grad = None
             (tcnn.mlp_torch(params, xg, cfg) * weight).sum().backward()
 
-        fns = {"torch_fwd": torch_fwd, "fused_fwd": fused_fwd, "fused_fwd_bwd": fused_fwd_bwd, "torch_fwd_bwd": torch_fwd_bwd}
+        def fused_step():
+            previous = tcnn.install_fused_backward(True)
+            try:
+                fused_fwd_bwd()
+            finally:
+                tcnn.install_fused_backward(previous)
+
+        fns = {"torch_fwd": torch_fwd, "fused_fwd": fused_fwd, "fused_fwd_bwd": fused_fwd_bwd, "torch_fwd_bwd": torch_fwd_bwd,
+               "fused_step": fused_step}
+        calls = tcnn.stats["hip_backward_calls"]
+        fused_step()
+        assert tcnn.stats["hip_backward_calls"] == calls + 1, "the fused backward did not run"
+        grads_fused = (xg.grad.clone(), params.grad.clone())
+        fused_fwd_bwd()
+        backward_agree = [float((a - b).abs().max()) for a, b in zip(grads_fused, (xg.grad, params.grad))]
         agree = float((fused_fwd() - torch_fwd()).abs().max())
         for fn in fns.values():        # warm up every variant
             for _ in range(3):
@@ -100,13 +115,16 @@ def main():
                 times[k].append(timed(fn, inner[k]))
         flops = 2.0 * pixels * (width * cfg.k0 + (layers - 1) * width * width + 3 * width)          # the arithmetic the model needs
         traffic = 4.0 * pixels * (features + 3 + 3)                                                   # input row + output row
-        entry = {"H": h, "W": w, "max_abs_diff_fused_vs_torch": agree, "forward_gflop": round(flops * 1e-9, 2), "forward_mbytes": round(traffic * 1e-6, 1)}
+        entry = {"H": h, "W": w, "max_abs_diff_fused_vs_torch": agree,
+                 "max_abs_diff_fused_backward_vs_torch_backward": {"grad_x": backward_agree[0], "grad_params": backward_agree[1]}, "forward_gflop": round(flops * 1e-9, 2), "forward_mbytes": round(traffic * 1e-6, 1)}
         for k, ts in times.items():
             entry[k] = {"ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4), "calls_per_window": inner[k]}
         entry["fused_fwd"]["tflops"] = round(flops / (entry["fused_fwd"]["ms"] * 1e-3) * 1e-12, 1)
         entry["fused_fwd"]["gbytes_per_s"] = round(traffic / (entry["fused_fwd"]["ms"] * 1e-3) * 1e-9, 1)
         entry["forward_ratio_torch_over_fused"] = round(entry["torch_fwd"]["ms"] / entry["fused_fwd"]["ms"], 2)
         entry["step_ratio_torch_over_fused"] = round(entry["torch_fwd_bwd"]["ms"] / entry["fused_fwd_bwd"]["ms"], 2)
+        entry["step_ratio_torch_over_fused_step"] = round(entry["torch_fwd_bwd"]["ms"] / entry["fused_step"]["ms"], 2)
+        entry["fused_step_over_fused_fwd"] = round(entry["fused_step"]["ms"] / entry["fused_fwd"]["ms"], 2)
         result["cases"][name] = entry
         del x, xg, weight, dirs
         torch.cuda.empty_cache()
