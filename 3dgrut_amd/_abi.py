@@ -153,6 +153,11 @@ class GrutMlpConfig(C.Structure):
                 ("n_output_dims", C.c_int32), ("output_activation", C.c_int32)]
 
 
+class GrutDecodeConfig(C.Structure):
+    """include/grut_amd.h: GrutDecodeConfig (the NHT decode stage around the network, grut_decode_forward)."""
+    _fields_ = [("mlp", GrutMlpConfig), ("sh_scale", C.c_float), ("unpremultiply_alpha", C.c_int32), ("center_ray", C.c_int32)]
+
+
 # every symbol include/grut_amd.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = [
     "gut_create", "gut_destroy", "gut_forward", "gut_backward", "gut_backward_unpacked", "gut_backward_factored", "gut_backward_factored_chunked", "grut_sph_grad_from_views", "gut_timings", "gut_stats",
@@ -170,6 +175,7 @@ EXPORTED_SYMBOLS = [
     "grut_ppisp_forward", "grut_ppisp_backward", "grut_ppisp_partials",
     "grut_mlp_forward", "grut_mlp_lds_bytes", "grut_mlp_num_params",
     "grut_mlp_backward", "grut_mlp_backward_lds_bytes", "grut_mlp_backward_scratch_bytes",
+    "grut_decode_forward", "grut_decode_backward",
     "grut_last_error", "grut_abi_version", "grut_set_allocator", "gut_trim", "grt_trim",
 ]
 
@@ -337,6 +343,12 @@ def _declare(lib):
     lib.grut_mlp_backward_lds_bytes.restype = C.c_uint32
     lib.grut_mlp_backward_scratch_bytes.argtypes = [C.POINTER(GrutMlpConfig), C.c_uint32]
     lib.grut_mlp_backward_scratch_bytes.restype = C.c_size_t
+    # stream, config, params, features [P, F], alpha [P] or NULL, rays_dir [P, 3] or NULL, rot [B, 9], num_views, pixels_per_view, out
+    lib.grut_decode_forward.argtypes = [vp, C.POINTER(GrutDecodeConfig), fp, fp, fp, fp, fp, C.c_uint32, C.c_uint32, fp]
+    lib.grut_decode_forward.restype = C.c_int
+    # .. pixels_per_view, grad_out, scratch, grad_features or NULL, grad_alpha or NULL, grad_params or NULL
+    lib.grut_decode_backward.argtypes = [vp, C.POINTER(GrutDecodeConfig), fp, fp, fp, fp, fp, C.c_uint32, C.c_uint32, fp, vp, fp, fp, fp]
+    lib.grut_decode_backward.restype = C.c_int
     lib.grut_last_error.argtypes = []
     lib.grut_last_error.restype = C.c_char_p
     lib.grut_abi_version.argtypes = []

@@ -1,6 +1,7 @@
 // mlp_backward.hip — the backward of the NHT decoder's network (mlp.hip) as ONE fused HIP kernel plus a small ordered reduction.
 // The contract: grut_mlp_backward in include/grut_amd.h.  Every index rule: mlp_layout.hpp ("the backward"), shared with the host emulation
-// of tests/test_mlp_backward_cpu.py.
+// of tests/test_mlp_backward_cpu.py.  The same kernel with another input source and gradient sink is the backward of the NHT decode stage
+// (grut_decode_backward): grad_features and grad_alpha instead of the gradient of assembled rows.
 //
 // Structure.  Persistent grid, one workgroup of four waves per CU; the workgroup builds the forward's bf16 weight image in LDS from the live
 // fp32 `params` and then takes 128 pixels per step, wave w the 32 pixels 32 w .. 32 w + 31.  Per step a wave
@@ -104,10 +105,17 @@ __device__ __forceinline__ void store_tile(float* __restrict__ dst, int rows, in
     }
 }
 
-template <int WIDTH, int NH, int KB0>
+// DECODE is the input source and the gradient sink: false, rows [P, F + 3] and grad_input [P, F + 3] through the SH
+// Jacobian (grut_mlp_backward); true, the decode stage (grut_decode_backward): `input` is the feature map [P, F], the direction comes from
+// decode_direction, grad_input is grad_features [P, F] (may be null) and grad_alpha [P] (may be null) takes the per-pixel sums.  `extra` is
+// empty for the rows, and (DecodeArgs, grad_alpha) for the decode stage.
+template <int WIDTH, int NH, int KB0, bool DECODE, class... Extra>
 __global__ __launch_bounds__(kBlock) void mlp_backward_kernel(Shape shape, int n_out, int activation, const float* __restrict__ params,
                                                               const float* __restrict__ input, const float* __restrict__ grad_out, uint32_t P,
-                                                              float* __restrict__ partials, float* __restrict__ grad_input) {
+                                                              float* __restrict__ partials, float* __restrict__ grad_input, Extra... extra) {
+    static_assert(sizeof...(Extra) == (DECODE ? 2 : 0), "(DecodeArgs, grad_alpha) for the decode stage, nothing for the rows");
+    const DecodeArgs da = decode_args(extra...);
+    float* const grad_alpha = decode_grad_alpha(extra...);
     constexpr int MB = WIDTH / kTile, KW = WIDTH / kStep;
     const Shape s{shape.n_features, shape.sh_degree, NH, WIDTH};   // the two template parameters as constants: most offsets fold
     constexpr int kSlotsH = (MB * MB + kBwdWaves - 1) / kBwdWaves, kSlots0 = (MB * KB0 + kBwdWaves - 1) / kBwdWaves;
@@ -120,9 +128,10 @@ __global__ __launch_bounds__(kBlock) void mlp_backward_kernel(Shape shape, int n
 
     const int lane = threadIdx.x & (GRUT_WAVE - 1), r = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / GRUT_WAVE));
-    const int nk0 = ksteps_first(s), kb0 = bwd_kblocks(s, 0), cols = s.n_features + 3;
+    const int nk0 = ksteps_first(s), kb0 = bwd_kblocks(s, 0), cols = DECODE ? s.n_features : s.n_features + 3;
     const int n_sh = s.sh_degree * s.sh_degree;
-    const bool need_p = partials != nullptr, need_x = grad_input != nullptr;
+    const bool need_p = partials != nullptr, need_x = grad_input != nullptr || (DECODE && grad_alpha != nullptr);
+    const bool unpremultiply = DECODE && da.unpremultiply;
 
     // the per-lane parts of every LDS address
     uint32_t st[2][2], rd[2], wt_first[KB0];
@@ -149,8 +158,16 @@ __global__ __launch_bounds__(kBlock) void mlp_backward_kernel(Shape shape, int n
     for (uint32_t step = blockIdx.x; step < steps; step += gridDim.x) {
         const uint64_t pixel = (uint64_t)step * kBwdPixels + (uint64_t)(kTile * wave + r);
         const bool valid = pixel < P;
-        const float* row = input + (valid ? pixel : (uint64_t)P - 1) * cols;   // a tail lane reads the last pixel, gets dZ = 0, stores nothing
-        const float dx_ = 2.f * row[s.n_features] - 1.f, dy_ = 2.f * row[s.n_features + 1] - 1.f, dz_ = 2.f * row[s.n_features + 2] - 1.f;
+        const uint64_t src = valid ? pixel : (uint64_t)P - 1;   // a tail lane reads the last pixel, gets dZ = 0, stores nothing
+        const float* row = input + src * cols;
+        float dir[3], alpha = 1.f, a_s = 1.f;
+        if constexpr (DECODE) {
+            decode_direction(da, decode_direction_load(da, (uint32_t)src), dir);
+            if (unpremultiply) alpha = da.alpha[src], a_s = fmaxf(alpha, 1e-8f);
+        } else {
+            dir[0] = 2.f * row[s.n_features] - 1.f, dir[1] = 2.f * row[s.n_features + 1] - 1.f, dir[2] = 2.f * row[s.n_features + 2] - 1.f;
+        }
+        const float dx_ = dir[0], dy_ = dir[1], dz_ = dir[2];
         const f32x16 sh = sh_values(dx_, dy_, dz_);
 
         // ---- 1. the forward again, with its rounding points; hb[l - 1] is the input of layer l ------------------------------------
@@ -161,7 +178,7 @@ __global__ __launch_bounds__(kBlock) void mlp_backward_kernel(Shape shape, int n
         const unsigned char* w = image + image_offset(s, 0, 0, 0, lane);
 #pragma nounroll
         for (int t = 0; t < nk0; ++t) {
-            const bf16x8 b = encode_step(s, t, h, row, sh);
+            const bf16x8 b = encode_step<DECODE>(s, t, h, row, sh, unpremultiply, a_s);
 #pragma unroll
             for (int m = 0; m < MB; ++m)
                 acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(*reinterpret_cast<const uint4*>(w + (size_t)frag_in_layer(nk0, m, t) * kFragBytes)),
@@ -189,6 +206,7 @@ __global__ __launch_bounds__(kBlock) void mlp_backward_kernel(Shape shape, int n
                                                         hb[NH - 1][t], o, 0, 0, 0);
 
         // ---- 2. the output layer: dZ = grad_out x the activation's derivative, fp32, then ONE rounding to bf16 ----------------------
+        float gy[8];   // DECODE: grad_out x the recomputed output after its activation, of this lane's output rows (for grad_alpha)
         {
             float g[8];
 #pragma unroll
@@ -203,6 +221,13 @@ __global__ __launch_bounds__(kBlock) void mlp_backward_kernel(Shape shape, int n
                 }
                 float go = 0.f;
                 if (valid && orow < n_out) go = grad_out[pixel * (uint64_t)n_out + orow];
+                if constexpr (DECODE) {
+                    float y = z;
+                    if (activation == GRUT_MLP_ACT_RELU) y = fmaxf(z, 0.f);
+                    if (activation == GRUT_MLP_ACT_SIGMOID) y = 1.f / (1.f + __expf(-z));
+                    gy[reg] = go * y;
+                    if (unpremultiply) go = go * a_s;   // the network's upstream gradient, formed before the derivative is applied
+                }
                 g[reg] = valid && orow < n_out ? go * d : 0.f;
             }
             dz[0] = as_frag(make_uint4(pack_bf16(g[0], g[1]), pack_bf16(g[2], g[3]), pack_bf16(g[4], g[5]), pack_bf16(g[6], g[7])));
@@ -255,7 +280,7 @@ __global__ __launch_bounds__(kBlock) void mlp_backward_kernel(Shape shape, int n
             for (int t = 0; t < KW; ++t) stage_store(stage_dz, t, st, dz[t]);
 #pragma nounroll
             for (int t = 0; t < nk0; ++t) {
-                const uint4 v = __builtin_bit_cast(uint4, encode_step(s, t, h, row, sh));
+                const uint4 v = __builtin_bit_cast(uint4, encode_step<DECODE>(s, t, h, row, sh, unpremultiply, a_s));
                 const uint32_t rest = bwd_stage_store_offset(0, t & ~1, 0, 0);
                 const uint32_t a0 = t & 1 ? st[1][0] : st[0][0], a1 = t & 1 ? st[1][1] : st[0][1];
                 *reinterpret_cast<uint2*>(stage_h + a0 + rest) = make_uint2(v.x, v.y);
@@ -274,6 +299,14 @@ __global__ __launch_bounds__(kBlock) void mlp_backward_kernel(Shape shape, int n
             float* ex = reinterpret_cast<float*>(stage_dz) + (size_t)(kTile * wave + r) * kExPitch;
             float* mine = reinterpret_cast<float*>(stage_dz) + (size_t)kBwdPixels * kExPitch + (size_t)(kTile * wave + r) * kShPitch;
             float* gx = grad_input + pixel * (uint64_t)cols;
+            const bool store_x = valid && (!DECODE || grad_input != nullptr), need_a = DECODE && grad_alpha != nullptr;
+            float sx = 0.f;   // DECODE: sum_j gx_j x_j, j ascending
+            if constexpr (DECODE) {
+                if (need_a) {   // (uniform) the SH slots are free here: they carry grad_out x y to ONE lane per pixel
+#pragma unroll
+                    for (int reg = 0; reg < 8; ++reg) mine[mlp_out_row(reg, h)] = gy[reg];
+                }
+            }
 #pragma unroll
             for (int kb = 0; kb < KB0; ++kb) {
                 if (kb >= kb0) break;   // (workgroup-uniform)
@@ -289,14 +322,29 @@ __global__ __launch_bounds__(kBlock) void mlp_backward_kernel(Shape shape, int n
                     const int k = kTile * kb + kStep * h + i;
                     const float v = ex[kStep * h + i];
                     if (k < s.n_features) {
-                        if (valid) gx[k] = v;
-                    } else if (k < s.n_features + n_sh) {
+                        if (store_x) gx[k] = unpremultiply ? v / a_s : v;
+                    } else if (!DECODE && k < s.n_features + n_sh) {
                         mine[k - s.n_features] = v;
+                    }
+                }
+                if constexpr (DECODE) {
+                    if (need_a) {   // (uniform) both lane halves of a pixel walk its 32 columns of this k block, in order
+#pragma nounroll
+                        for (int i = 0; i < kTile; ++i) {
+                            const int k = kTile * kb + i;
+                            if (k < s.n_features) sx += ex[i] * (row[k] / a_s);   // x_k: the fp32 column the network saw, before its bf16 rounding
+                        }
                     }
                 }
                 __syncthreads();
             }
-            if (h == 0 && valid) {   // the SH Jacobian and the 2 of d = 2 u - 1, fp32, in the fixed order of the SH index
+            if constexpr (DECODE) {
+                if (need_a && h == 0 && valid) {
+                    float sy = 0.f;
+                    for (int c = 0; c < n_out; ++c) sy += mine[c];
+                    grad_alpha[pixel] = alpha >= 1e-8f ? sy - sx / a_s : 0.f;   // the gate of a_s = max(alpha, 1e-8f), inclusive
+                }
+            } else if (h == 0 && valid) {   // the SH Jacobian and the 2 of d = 2 u - 1, fp32, in the fixed order of the SH index
                 const float x = dx_, y = dy_, z = dz_, xx = x * x, yy = y * y, zz = z * z;
                 float jx = 0.f, jy = 0.f, jz = 0.f;
                 if (s.sh_degree >= 2) {
@@ -363,18 +411,26 @@ __global__ __launch_bounds__(256) void mlp_backward_reduce_kernel(const float* _
 constexpr int kMaxLayers = 5;
 bool taken(const Shape& s) { return s.n_hidden_layers <= kMaxLayers && bwd_lds_bytes(s) != 0; }
 
-template <int WIDTH, int NH, int KB0>
+template <int WIDTH, int NH, int KB0, bool DECODE>
 int launch(hipStream_t stream, const Shape& s, const GrutMlpConfig* c, const float* params, const float* input, const float* grad_out,
-           uint32_t P, float* scratch, float* grad_input, float* grad_params) {
+           uint32_t P, float* scratch, float* grad_input, float* grad_params, const DecodeArgs& da, float* grad_alpha) {
     int dev = 0, cus = 0;
     GRUT_HIP(hipGetDevice(&dev));
     GRUT_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     const uint32_t bytes = bwd_lds_bytes(s), grid = bwd_grid(P, (uint32_t)(cus > 0 ? cus : 1));
-    if (bytes > 64u * 1024u)
-        GRUT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_backward_kernel<WIDTH, NH, KB0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)bytes));
-    mlp_backward_kernel<WIDTH, NH, KB0><<<grid, kBlock, bytes, stream>>>(s, c->n_output_dims, c->output_activation, params, input, grad_out, P,
-                                                                    grad_params ? scratch : nullptr, grad_input);
+    if constexpr (DECODE) {
+        if (bytes > 64u * 1024u)
+            GRUT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_backward_kernel<WIDTH, NH, KB0, true, DecodeArgs, float*>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        mlp_backward_kernel<WIDTH, NH, KB0, true, DecodeArgs, float*><<<grid, kBlock, bytes, stream>>>(
+            s, c->n_output_dims, c->output_activation, params, input, grad_out, P, grad_params ? scratch : nullptr, grad_input, da, grad_alpha);
+    } else {
+        if (bytes > 64u * 1024u)
+            GRUT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_backward_kernel<WIDTH, NH, KB0, false>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        mlp_backward_kernel<WIDTH, NH, KB0, false><<<grid, kBlock, bytes, stream>>>(s, c->n_output_dims, c->output_activation, params, input, grad_out, P,
+                                                                               grad_params ? scratch : nullptr, grad_input);
+    }
     GRUT_HIP(hipGetLastError());
     if (grad_params) {
         const uint32_t n = num_params(s);
@@ -382,6 +438,33 @@ int launch(hipStream_t stream, const Shape& s, const GrutMlpConfig* c, const flo
         GRUT_HIP(hipGetLastError());
     }
     return GRUT_OK;
+}
+
+
+// the kernel's template parameters: width, hidden layers, and the first layer's k blocks at most (its dW tiles are registers)
+template <bool DECODE>
+int dispatch(hipStream_t st, const Shape& s, const GrutMlpConfig* config, const float* params, const float* input, const float* grad_out,
+             uint32_t P, float* sc, float* grad_input, float* grad_params, const DecodeArgs& da, float* grad_alpha) {
+    const int kb0 = s.width == 128 ? bwd_kblocks(s, 0) : kMaxK0 / kTile;
+#define GRUT_MLP_BWD(W, N, K) \
+    if (s.width == W && s.n_hidden_layers == N && kb0 == K) \
+    return launch<W, N, K, DECODE>(st, s, config, params, input, grad_out, P, sc, grad_input, grad_params, da, grad_alpha)
+#define GRUT_MLP_BWD_128(N) GRUT_MLP_BWD(128, N, 1); GRUT_MLP_BWD(128, N, 2); GRUT_MLP_BWD(128, N, 3); GRUT_MLP_BWD(128, N, 4)
+    GRUT_MLP_BWD(64, 1, 4);
+    GRUT_MLP_BWD(64, 2, 4);
+    GRUT_MLP_BWD(64, 3, 4);
+    GRUT_MLP_BWD(64, 4, 4);
+    GRUT_MLP_BWD(64, 5, 4);
+    GRUT_MLP_BWD_128(1);
+    GRUT_MLP_BWD_128(2);
+    GRUT_MLP_BWD(128, 3, 1);
+    GRUT_MLP_BWD(128, 3, 2);
+    GRUT_MLP_BWD(128, 3, 3);   // (K0 > 96 with 3 layers of 128 does not fit into LDS)
+#undef GRUT_MLP_BWD_128
+#undef GRUT_MLP_BWD
+    set_last_error("%s: no kernel for width %d with %d hidden layers", DECODE ? "grut_decode_backward" : "grut_mlp_backward", s.width,
+                   s.n_hidden_layers);
+    return GRUT_ERR_BAD_INPUT;
 }
 
 }  // namespace
@@ -411,26 +494,26 @@ extern "C" int grut_mlp_backward(void* stream, const GrutMlpConfig* config, cons
     GRUT_REQUIRE(P > 0 && params && input && grad_out, "grut_mlp_backward: num_pixels > 0, params, input and grad_out are required");
     GRUT_REQUIRE(!grad_params || scratch, "grut_mlp_backward: grad_params needs the scratch of grut_mlp_backward_scratch_bytes");
     GRUT_REQUIRE(((uintptr_t)params & 15u) == 0, "grut_mlp_backward: params must be 16-byte aligned");
-    const hipStream_t st = (hipStream_t)stream;
-    float* sc = static_cast<float*>(scratch);
-    // the kernel's template parameters: width, hidden layers, and the first layer's k blocks at most (its dW tiles are registers)
-    const int kb0 = s.width == 128 ? bwd_kblocks(s, 0) : kMaxK0 / kTile;
-#define GRUT_MLP_BWD(W, N, K) \
-    if (s.width == W && s.n_hidden_layers == N && kb0 == K) \
-    return launch<W, N, K>(st, s, config, params, input, grad_out, P, sc, grad_input, grad_params)
-#define GRUT_MLP_BWD_128(N) GRUT_MLP_BWD(128, N, 1); GRUT_MLP_BWD(128, N, 2); GRUT_MLP_BWD(128, N, 3); GRUT_MLP_BWD(128, N, 4)
-    GRUT_MLP_BWD(64, 1, 4);
-    GRUT_MLP_BWD(64, 2, 4);
-    GRUT_MLP_BWD(64, 3, 4);
-    GRUT_MLP_BWD(64, 4, 4);
-    GRUT_MLP_BWD(64, 5, 4);
-    GRUT_MLP_BWD_128(1);
-    GRUT_MLP_BWD_128(2);
-    GRUT_MLP_BWD(128, 3, 1);
-    GRUT_MLP_BWD(128, 3, 2);
-    GRUT_MLP_BWD(128, 3, 3);   // (K0 > 96 with 3 layers of 128 does not fit into LDS)
-#undef GRUT_MLP_BWD_128
-#undef GRUT_MLP_BWD
-    set_last_error("grut_mlp_backward: no kernel for width %d with %d hidden layers", s.width, s.n_hidden_layers);
-    return GRUT_ERR_BAD_INPUT;
+    return dispatch<false>((hipStream_t)stream, s, config, params, input, grad_out, P, static_cast<float*>(scratch), grad_input, grad_params,
+                           DecodeArgs{}, nullptr);
+}
+
+extern "C" int grut_decode_backward(void* stream, const GrutDecodeConfig* config, const float* params, const float* features, const float* alpha,
+                                    const float* rays_dir, const float* rot, uint32_t num_views, uint32_t pixels_per_view, const float* grad_out,
+                                    void* scratch, float* grad_features, float* grad_alpha, float* grad_params) {
+    Shape s;
+    DecodeArgs da;
+    uint32_t P = 0;
+    if (!decode_args_of("grut_decode_backward", config, alpha, rays_dir, rot, num_views, pixels_per_view, &da, &P)) return GRUT_ERR_BAD_INPUT;
+    GRUT_REQUIRE(shape_of(&config->mlp, &s), "grut_decode_backward: width must be 64 or 128, sh_degree 1..4, n_hidden_layers >= 1, the padded encoded "
+                                             "width at most 128, n_output_dims 1..16 and the activation one of GRUT_MLP_ACT_*");
+    GRUT_REQUIRE(taken(s), "grut_decode_backward: the weight image and the two staged tiles of this configuration do not fit into LDS, or it "
+                           "has more than 5 hidden layers (grut_mlp_backward_lds_bytes)");
+    GRUT_REQUIRE(grad_features || grad_alpha || grad_params, "grut_decode_backward: grad_features, grad_alpha and grad_params are all NULL, nothing to compute");
+    GRUT_REQUIRE(!grad_alpha || config->unpremultiply_alpha, "grut_decode_backward: grad_alpha needs unpremultiply_alpha (alpha has no gradient without it)");
+    GRUT_REQUIRE(params && grad_out && (features || s.n_features == 0), "grut_decode_backward: params, features and grad_out are required");
+    GRUT_REQUIRE(!grad_params || scratch, "grut_decode_backward: grad_params needs the scratch of grut_mlp_backward_scratch_bytes");
+    GRUT_REQUIRE(((uintptr_t)params & 15u) == 0, "grut_decode_backward: params must be 16-byte aligned");
+    return dispatch<true>((hipStream_t)stream, s, &config->mlp, params, features, grad_out, P, static_cast<float*>(scratch), grad_features, grad_params,
+                          da, grad_alpha);
 }

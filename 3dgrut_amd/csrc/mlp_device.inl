@@ -1,5 +1,5 @@
 // mlp_device.inl — what the decoder MLP's forward (mlp.hip) and backward (mlp_backward.hip) share on the device: the fragment types, the
-// bf16 pack, the SH polynomials and the first layer's encoded-input fragment.  Included inside namespace grut's anonymous namespace, after
+// bf16 pack, the SH polynomials, the decode stage's direction and the first layer's encoded-input fragment.  Included inside namespace grut's anonymous namespace, after
 // common.hpp and mlp_layout.hpp.
 
 using namespace grut_mlp;
@@ -47,19 +47,78 @@ __device__ __forceinline__ float sh_or_one(int e, const f32x16& sh) {
     return e == kInputOne ? 1.f : v;
 }
 
+// ---- the decode stage (grut_decode_forward / grut_decode_backward): where a pixel's direction and alpha come from ---------------------------
+struct DecodeArgs {
+    const float* alpha;          // [P]; read only with unpremultiply
+    const float* rays;           // [P, 3] camera space; not read with center_ray
+    const float* rot;            // [B, 9] row-major camera-to-world rotations
+    uint32_t pixels_per_view;
+    float sh_scale;
+    int unpremultiply, center_ray;
+};
+
+// the kernels' trailing arguments: none for the rows [P, F + 3]; for the decode stage one DecodeArgs and, in the backward, grad_alpha
+__device__ __forceinline__ DecodeArgs decode_args() { return DecodeArgs{}; }
+__device__ __forceinline__ DecodeArgs decode_args(const DecodeArgs& a, float* = nullptr) { return a; }
+__device__ __forceinline__ float* decode_grad_alpha() { return nullptr; }
+__device__ __forceinline__ float* decode_grad_alpha(const DecodeArgs&, float* grad_alpha) { return grad_alpha; }
+
+// What decode_direction reads of pixel `pixel` (< P: a tail lane passes the last pixel): the rotation of its view (per lane: a tile may
+// straddle two views) and, unless center_ray, its camera ray.  Apart from the arithmetic, so that the forward can issue these loads one
+// step ahead.
+struct DirectionInput {
+    float R[9], c[3];
+};
+__device__ __forceinline__ DirectionInput decode_direction_load(const DecodeArgs& a, uint32_t pixel) {
+    DirectionInput in;
+    const float* R = a.rot + (size_t)(pixel / a.pixels_per_view) * 9;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) in.R[i] = R[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) in.c[i] = a.center_ray ? 0.f : a.rays[(size_t)pixel * 3 + i];   // (uniform)
+    return in;
+}
+
+// d = 2 u - 1: u = (n sh_scale + 1) 0.5, n = w / max(|w|, 1e-12), w = R_b d_cam or, with center_ray, column 2 of R_b.  ONE function for the
+// forward and the backward's recomputation.  sqrtf and / are the correctly rounded IEEE operations (hipcc's default,
+// -fhip-fp32-correctly-rounded-divide-sqrt): no reciprocal anywhere.
+__device__ __forceinline__ void decode_direction(const DecodeArgs& a, const DirectionInput& in, float (&d)[3]) {
+    float w[3];
+    if (a.center_ray) {   // (uniform)
+        w[0] = in.R[2], w[1] = in.R[5], w[2] = in.R[8];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) w[i] = in.R[3 * i] * in.c[0] + in.R[3 * i + 1] * in.c[1] + in.R[3 * i + 2] * in.c[2];
+    }
+    const float len = fmaxf(sqrtf(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]), 1e-12f);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float u = ((w[i] / len) * a.sh_scale + 1.f) * 0.5f;
+        d[i] = 2.f * u - 1.f;
+    }
+}
+
 // the B fragment of k-step t of the first layer: 8 elements of this lane's pixel, in the order of mlp_input_element.  Which kind of
 // element j is depends on the lane half only, so both halves' kinds are wave-uniform and the lane picks its own by h.
-__device__ __forceinline__ bf16x8 encode_step(const Shape& s, int t, int h, const float* __restrict__ row, const f32x16& sh) {
+// DECODE: `row` is the pixel's F feature columns alone, and with `unpremultiply` (uniform) a feature column is row[e] / a_s, an IEEE division.
+template <bool DECODE = false>
+__device__ __forceinline__ bf16x8 encode_step(const Shape& s, int t, int h, const float* __restrict__ row, const f32x16& sh,
+                                              bool unpremultiply = false, float a_s = 1.f) {
     float v[8];
     if (kStep * (t + 1) <= s.n_features) {   // (wave-uniform) all 16 elements are feature columns
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = row[mlp_input_element(s, t, h, j)];
+        if (DECODE && unpremultiply) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = v[j] / a_s;
+        }
     } else {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int e0 = mlp_input_element(s, t, 0, j), e1 = mlp_input_element(s, t, 1, j), e = h ? e1 : e0;
             const float other = h ? sh_or_one(e1, sh) : sh_or_one(e0, sh);
-            const float feature = row[e > 0 ? e : 0];
+            float feature = DECODE && s.n_features == 0 ? 0.f : row[e > 0 ? e : 0];   // (no feature column at all: nothing to read)
+            if (DECODE && unpremultiply) feature = feature / a_s;
             v[j] = e >= 0 ? feature : other;
         }
     }
@@ -107,4 +166,24 @@ inline bool shape_of(const GrutMlpConfig* c, Shape* s) {
     *s = Shape{c->n_features, c->sh_degree, c->n_hidden_layers, c->width};
     return shape_ok(*s) && c->n_output_dims >= 1 && c->n_output_dims <= kOutRows && c->output_activation >= GRUT_MLP_ACT_NONE &&
            c->output_activation <= GRUT_MLP_ACT_SIGMOID;
+}
+
+// the checks that grut_decode_forward and grut_decode_backward share, and their kernel arguments; P = num_views * pixels_per_view
+inline bool decode_args_of(const char* who, const GrutDecodeConfig* c, const float* alpha, const float* rays_dir, const float* rot,
+                           uint32_t num_views, uint32_t pixels_per_view, DecodeArgs* da, uint32_t* P) {
+    if (!c || !rot || num_views == 0 || pixels_per_view == 0 || (uint64_t)num_views * pixels_per_view > 0xffffffffull) {
+        set_last_error("%s: config, rot, num_views > 0, pixels_per_view > 0 and num_views * pixels_per_view < 2^32 are required", who);
+        return false;
+    }
+    if (c->unpremultiply_alpha && !alpha) {
+        set_last_error("%s: unpremultiply_alpha needs alpha", who);
+        return false;
+    }
+    if (!c->center_ray && !rays_dir) {
+        set_last_error("%s: rays_dir may be NULL only with center_ray", who);
+        return false;
+    }
+    *da = DecodeArgs{alpha, rays_dir, rot, pixels_per_view, c->sh_scale, c->unpremultiply_alpha != 0, c->center_ray != 0};
+    *P = num_views * pixels_per_view;
+    return true;
 }

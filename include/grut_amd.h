@@ -750,6 +750,49 @@ size_t grut_mlp_backward_scratch_bytes(const GrutMlpConfig* config, uint32_t num
 int grut_mlp_backward(void* stream, const GrutMlpConfig* config, const float* params, const float* input, const float* grad_out,
                       uint32_t num_pixels, void* scratch, float* grad_input, float* grad_params);
 
+/* The decode stage around that network (threedgrut/utils/render.py: apply_feature_decoder, and FeatureDecoder._process of
+ * threedgrut/model/feature_decoder.py) in the SAME pass: the kernel of grut_mlp_forward with another input source.  No [P, F + 3] rows exist.
+ *   inputs  P = num_views * pixels_per_view < 2^32 pixels, all contiguous fp32 DEVICE:
+ *             features [P, F]   alpha [P] (may be NULL)   rays_dir [P, 3] camera space (NULL only with center_ray)
+ *             rot [num_views, 9] row-major T_to_world[:, :3, :3]
+ *   direction  of a pixel of view b = pixel / pixels_per_view: w = R_b d_cam (fp32 sums, contraction free), or with center_ray column 2 of
+ *           R_b; n = w / max(|w|, 1e-12) with a correctly rounded square root and IEEE divisions (no reciprocal);
+ *           u = (n * sh_scale + 1) * 0.5; the network sees d = 2 u - 1 as grut_mlp_forward does.  One device function for the forward and
+ *           the backward's recomputation.
+ *   unpremultiply_alpha  (needs alpha) a_s = max(alpha, 1e-8f); the network's feature columns are features / a_s (IEEE division, before
+ *           the bf16 rounding of the encoded input), the result is y * a_s.  Without the flag alpha is not read.
+ *   network everything from the encoded input on is grut_mlp_forward's contract and its code: rounding points, layer order, activation.
+ *           On inputs where every direction operation is exact, the result equals grut_mlp_forward on the assembled rows bit for bit.
+ *   out     [P, n_output_dims]
+ * One launch; no allocation, no synchronisation, no atomics; `params` is read live at every launch.  The configurations of grut_mlp_forward;
+ * anything else, a missing pointer or P >= 2^32 is GRUT_ERR_BAD_INPUT before a launch. */
+typedef struct GrutDecodeConfig {
+    GrutMlpConfig mlp;
+    float sh_scale;
+    int32_t unpremultiply_alpha;
+    int32_t center_ray;
+} GrutDecodeConfig;
+int grut_decode_forward(void* stream, const GrutDecodeConfig* config, const float* params, const float* features, const float* alpha,
+                        const float* rays_dir, const float* rot, uint32_t num_views, uint32_t pixels_per_view, float* out);
+
+/* The backward of grut_decode_forward: the kernel of grut_mlp_backward with that input source and another gradient sink.  Each of
+ * grad_features [P, F], grad_alpha [P] and grad_params may be NULL; all NULL, or grad_alpha without unpremultiply_alpha, is
+ * GRUT_ERR_BAD_INPUT.  Rays and poses get no gradient.  The rules of grut_mlp_backward, and:
+ *   upstream  the network's upstream gradient is grad_out * a_s with unpremultiply_alpha (formed first; the activation's derivative is
+ *           applied to that product), otherwise grad_out.
+ *   gx      the fp32 gradient of the network's feature columns; the SH Jacobian is not evaluated.
+ *           grad_features = gx / a_s (IEEE division) with unpremultiply_alpha, otherwise gx.
+ *   grad_alpha = [alpha >= 1e-8f] * (sum_c grad_out_c y_c - (sum_j gx_j x_j) / a_s), fp32: x_j = features_j / a_s, the fp32 feature column
+ *           before its bf16 rounding; y the recomputed fp32 output after its activation (before the product with a_s).  Both sums start
+ *           from 0 and add one product at a time (possibly fused), j = 0 .. F - 1 ascending, then c = 0 .. n_output_dims - 1 ascending.
+ *           The gate is inclusive, as the gradient of torch.clamp is; where it is closed the result is +0.0.
+ *   order   grid, partials, reduction order and scratch of grut_mlp_backward (grut_mlp_backward_scratch_bytes and
+ *           grut_mlp_backward_lds_bytes apply as they are): two calls are bitwise equal, and grad_features and grad_alpha do not depend on
+ *           whether grad_params is asked for. */
+int grut_decode_backward(void* stream, const GrutDecodeConfig* config, const float* params, const float* features, const float* alpha,
+                         const float* rays_dir, const float* rot, uint32_t num_views, uint32_t pixels_per_view, const float* grad_out,
+                         void* scratch, float* grad_features, float* grad_alpha, float* grad_params);
+
 /* ---- nearest-neighbour initialisation (threedgrut/model/geometry.py) ----------------------------------------------- */
 /* Exact k nearest neighbours in 3-D, the device side of what the reference's initialisation takes from sklearn.neighbors:
  * k_nearest_neighbors (geometry.py:42-49, called at model.py:732 for the Gaussians' initial size), nearest_neighbors (geometry.py:52-73)
