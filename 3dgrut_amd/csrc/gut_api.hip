@@ -36,7 +36,11 @@ struct GutHandle {
     DeviceBuffer tiles_count, proj_pos, conic_opacity, extent, depth, rgb, depth_key, particle_idx;
     DeviceBuffer depth_key_tmp, particle_idx_tmp, offsets, sort_scratch, scan_scratch, counters;
     DeviceBuffer rec64;   // [N][4] float4: the per-particle 64-byte records of the direct tile lists (GutParams::rec64)
-    DeviceBuffer part_offset, pos_particle, grad_partial, grad_flag, g_rgb, poses_dev, walk8;
+    DeviceBuffer part_offset, pos_particle, grad_partial, grad_flag, grad_touched, g_rgb, poses_dev, walk8;
+    // the gradient sweep's marks (grad_touched, grad_flag: GutGradSlots) are all zero whenever no backward is in flight: zeroed when
+    // (re)allocated, cleared again by the finalisation that reads them.  Set while a backward's launches are being enqueued; a backward
+    // that finds it set (the previous one failed half way) clears both arrays first
+    bool flags_dirty = false;
     // per-intersection scratch
     DeviceBuffer tile_keys, tile_vals, tile_keys_tmp, tile_vals_tmp, tile_sort_scratch, ranges;
     DeviceBuffer ck_tc, ck_d, ck_reached, ck_boundary_tile, ck_nht;
@@ -271,6 +275,7 @@ static void release_scratch(GutHandle* h) {
     DeviceBuffer* bufs[] = {&h->tiles_count, &h->proj_pos, &h->conic_opacity, &h->extent, &h->depth, &h->rgb, &h->depth_key,
                             &h->particle_idx, &h->depth_key_tmp, &h->particle_idx_tmp, &h->offsets, &h->sort_scratch,
                             &h->scan_scratch, &h->counters, &h->rec64, &h->walk8, &h->part_offset, &h->pos_particle, &h->grad_partial, &h->grad_flag,
+                            &h->grad_touched,
                             &h->g_rgb, &h->poses_dev, &h->work_counters, &h->tile_keys, &h->tile_vals, &h->tile_keys_tmp,
                             &h->tile_vals_tmp, &h->tile_sort_scratch, &h->ranges, &h->ck_tc, &h->ck_d, &h->ck_nht, &h->ck_reached,
                             &h->ck_boundary_tile};
@@ -290,6 +295,7 @@ int gut_trim(GutHandle* h) {
     h->sorted_pos = nullptr;
     h->sorted_tile_keys = nullptr;
     h->work_pending = false;
+    h->flags_dirty = false;   // (the marks are gone with their buffers; new ones start zeroed)
     h->ck_boundaries_capacity = 0;
     memset(&h->checkpoints, 0, sizeof(h->checkpoints));
     return GRUT_OK;
@@ -481,6 +487,22 @@ int gut_forward(GutHandle* h, void* stream_, const GutFrame* frame, const float*
     return GRUT_OK;
 }
 
+// The gradient slots of a backward over I tile entries: the partials and both levels of marks (GutGradSlots).  Marks are not cleared per
+// backward - the finalisation leaves them zero - only when their buffer is new (first use, growth, after gut_trim) or the handle is dirty.
+static int prepare_grad_slots(GutHandle* h, hipStream_t s, size_t I, GutGradSlots& slots) {
+    const size_t touched_bytes = h->grad_touched.bytes, flag_bytes = h->grad_flag.bytes;
+    GRUT_CHECK(h->grad_partial.ensure(2 * I * (size_t)slots.stride * 4, 1.3f));
+    GRUT_CHECK(h->grad_touched.ensure((size_t)h->params.N * 8, 1.25f));
+    GRUT_CHECK(h->grad_flag.ensure(2 * I, 1.3f));
+    if (h->flags_dirty || h->grad_touched.bytes != touched_bytes) GRUT_HIP(hipMemsetAsync(h->grad_touched.ptr, 0, h->grad_touched.bytes, s));
+    if (h->flags_dirty || h->grad_flag.bytes != flag_bytes) GRUT_HIP(hipMemsetAsync(h->grad_flag.ptr, 0, h->grad_flag.bytes, s));
+    h->flags_dirty = true;   // until the finalisation that cleans up is enqueued
+    slots.partial = h->grad_partial.as<float>();
+    slots.touched = h->grad_touched.as<unsigned long long>();
+    slots.flag = h->grad_flag.as<uint8_t>();
+    return GRUT_OK;
+}
+
 // gut_backward / gut_backward_factored: exactly one of grad_particle_sph and grad_radiance is non-null
 static int backward_impl(GutHandle* h, void* stream_, const GutFrame* frame, const float* particle_density, const void* particle_sph_,
                          const float* ray_origin, const float* ray_direction, const void* feat_density_, const float* grad_feat_density,
@@ -533,14 +555,12 @@ static int backward_impl(GutHandle* h, void* stream_, const GutFrame* frame, con
             GutGradSlots slots;
             slots.stride = 16;
             slots.partial = nullptr;
+            slots.touched = nullptr;
             slots.flag = nullptr;
             slots.pos_particle = h->pos_particle.as<uint32_t>();
+            slots.part_offset = proj.part_offset;
             if (I > 0) {
-                GRUT_CHECK(h->grad_partial.ensure(2 * I * (size_t)slots.stride * 4, 1.3f));
-                GRUT_CHECK(h->grad_flag.ensure(2 * I + 96, 1.3f));
-                slots.partial = h->grad_partial.as<float>();
-                slots.flag = h->grad_flag.as<uint8_t>();
-                GRUT_HIP(hipMemsetAsync(slots.flag, 0, 2 * I, s));
+                GRUT_CHECK(prepare_grad_slots(h, s, I, slots));
                 GRUT_CHECK(h->stage_begin(GUT_STAGE_RENDER_BWD, s, slot));
                 launch_render_nhtp_bwd(s, P, h->ranges.as<uint32_t>(), h->sorted_pos, particle_density, particle_sph, ray_origin, ray_direction, feat_density,
                                        io ? nullptr : grad_feat_density, io ? io->grad_features : nullptr, io ? io->grad_opacity : nullptr, hit_distance,
@@ -550,6 +570,8 @@ static int backward_impl(GutHandle* h, void* stream_, const GutFrame* frame, con
             GRUT_CHECK(h->stage_begin(GUT_STAGE_PROJECT_BWD, s, slot));
             launch_grad_finalize_nht(s, P, proj, particle_density, slots, I > 0, g_out);
             GRUT_CHECK(h->stage_end(GUT_STAGE_PROJECT_BWD, s, slot));
+            GRUT_HIP(hipGetLastError());
+            h->flags_dirty = false;
         } else {
             GRUT_HIP(hipMemsetAsync(grad_particle_density, 0, (size_t)P.N * 48, s));
             if (I > 0)
@@ -581,8 +603,10 @@ static int backward_impl(GutHandle* h, void* stream_, const GutFrame* frame, con
     GutGradSlots slots;
     slots.stride = has_gdist ? 20 : 16;
     slots.partial = nullptr;
+    slots.touched = nullptr;
     slots.flag = nullptr;
     slots.pos_particle = h->pos_particle.as<uint32_t>();
+    slots.part_offset = proj.part_offset;
     const size_t I = h->num_intersections;
     if (P.k_buffer > 0) {
         // sorted mode: per-hit atomics like the reference (gutKBufferRenderer.cuh:158-198), then the projection backward
@@ -604,12 +628,8 @@ static int backward_impl(GutHandle* h, void* stream_, const GutFrame* frame, con
         return GRUT_OK;
     }
     if (I > 0) {
-        // one slot per (tile entry, half tile); only flagged slots are ever read, so only the flags are cleared
-        GRUT_CHECK(h->grad_partial.ensure(2 * I * (size_t)slots.stride * 4, 1.3f));
-        GRUT_CHECK(h->grad_flag.ensure(2 * I + 96, 1.3f));  // + slack: flags are scanned 64 at a time
-        slots.partial = h->grad_partial.as<float>();
-        slots.flag = h->grad_flag.as<uint8_t>();
-        GRUT_HIP(hipMemsetAsync(slots.flag, 0, 2 * I, s));
+        // one slot per (tile entry, half tile); only marked slots are ever read, and the marks are zero already
+        GRUT_CHECK(prepare_grad_slots(h, s, I, slots));
         GRUT_CHECK(h->stage_begin(GUT_STAGE_RENDER_BWD, s, slot));
         launch_render_bwd(s, P, h->ranges.as<uint32_t>(), h->sorted_pos, particle_density, proj.rgb, ray_origin, ray_direction, feat_density,
                           g_in, hit_distance, grad_hit_distance, slots, h->checkpoints);
@@ -635,6 +655,7 @@ static int backward_impl(GutHandle* h, void* stream_, const GutFrame* frame, con
     }
     GRUT_CHECK(h->stage_end(GUT_STAGE_PROJECT_BWD, s, slot));
     GRUT_HIP(hipGetLastError());
+    h->flags_dirty = false;   // every particle's finalisation is enqueued: it leaves the marks zero
     if (h->cfg.enable_kernel_timings) GRUT_CHECK(h->bwd_timer.end(s));
     return GRUT_OK;
 }

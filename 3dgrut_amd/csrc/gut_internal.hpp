@@ -56,14 +56,23 @@ struct GutProjected {
 
 // Gradient partials of the compositing sweep.  Tile entries are identified by their position q in EXPANSION order
 // (particle-major: particle p owns [part_offset[p], part_offset[p] + tiles_count[p])).  Each (entry, half tile) task
-// that hit the particle writes its wave-reduced gradient terms to slot q*2 + half and raises the slot's flag, so
-// the per-particle gather (gut_grad_finalize) sums a contiguous range: no atomics, bitwise reproducible gradients.
+// that hit the particle writes its wave-reduced gradient terms to slot q*2 + half and marks the slot as written, so
+// the per-particle gather (gut_grad_finalize) sums a contiguous range: no float atomics, bitwise reproducible gradients.
+// The marks are kept on two levels.  A particle's first 32 tile entries (ordinal = q - part_offset[p] < 32) are bits of ONE word per
+// particle: bit 2 ordinal + half of touched[p], set with an atomic OR (bits of one word are set by different waves) and read by the
+// finalisation with one coalesced load next to tiles_count / part_offset.  Later entries (only particles that cover more than 32
+// tiles have any) keep one byte per slot in flag[], indexed by the slot.  Which level a slot uses depends on its ordinal alone.
+// Invariant: both arrays are all zero whenever no backward is in flight on the handle - the finalisation clears what it read
+// (every particle is finalised exactly once per backward), so nothing is cleared ahead of the sweep (GutHandle::flags_dirty).
 struct GutGradSlots {
     float* partial;              // [2 I][stride]  {B(3), d density, M(9), d radiance(3)} (+ direct scale terms, pad)
-    uint8_t* flag;               // [2 I]          zeroed before every gradient sweep
+    unsigned long long* touched; // [N]            bit 2 ordinal + half: slot 2 (part_offset + ordinal) + half was written (ordinal < 32)
+    uint8_t* flag;               // [2 I]          the same for the slots of ordinals >= 32
     const uint32_t* pos_particle;// [I]            particle of expansion position q (0xFFFFFFFF = padding)
+    const uint32_t* part_offset; // [N]            GutProjected::part_offset (legacy lists: ordinal = q - part_offset[particle])
     int stride;                  // floats per slot: 16, or 20 when a depth gradient flows in
 };
+constexpr uint32_t kGutTouchBits = 64;   // slots per particle marked in touched[]
 
 // Where the geometric particle gradient goes: the reference's packed [N,12] rows, or (packed == nullptr) the model's four
 // tensors directly — positions [N,3], density [N,1], rotation [N,4], scale [N,3] — which saves the caller the unpack pass.

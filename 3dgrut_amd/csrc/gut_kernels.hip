@@ -446,7 +446,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, GRUT_PRO
         has_tiles = ntiles > 0;
         if (has_tiles && out.walk8)   // {minx : 12 | miny : 12 | width - 1 : 3 | height - 1 : 3 | kind : 2, keep mask}; kind 0 = the expansion walks the box itself
             out.walk8[i] = make_uint2((uint32_t)bb.minx | ((uint32_t)bb.miny << 12) | ((uint32_t)(bb.maxx - bb.minx - 1) & 7u) << 24 |
-                                          ((uint32_t)(bb.maxy - bb.miny - 1) & 7u) << 27 | ((ex <= 1e-06f ? 0u : walk_kind) << 30), walk_mask);   // (an extent the expansion skips, gutProjector.cuh:344-348: its own path)
+                                          ((uint32_t)(bb.maxy - bb.miny - 1) & 7u) << 27 | ((ex <= 1e-06f ? 0u : walk_kind) << 30), ex <= 1e-06f ? 0u : walk_mask);   // (an extent the expansion skips, gutProjector.cuh:344-348: kind 0, nothing kept)
         if (!has_tiles) {
             out.proj_pos[i] = make_float2(0.f, 0.f);
             out.conic_opacity[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -569,7 +569,7 @@ __global__ __launch_bounds__(256) void gut_expand_kernel(GutParams P, GutProject
             if (direct) reinterpret_cast<uint32_t*>(proj.rec64 + 4 * (size_t)p + 2)[3] = off;
             const uint2 w8 = cached_walks ? proj.walk8[p] : make_uint2(0u, 0u);
             walk_kind = w8.x >> 30;
-            walk_mask = w8.y;
+            walk_mask = walk_kind != 0u ? w8.y : 0u;   // (a mask belongs to a one-step walk; an extent <= 1e-6 keeps the empty box below: padding only)
             if (walk_kind != 0u) {   // the counting pass's one-step walk: box and keep mask as it left them
                 bb.minx = (int)(w8.x & 0xFFFu); bb.miny = (int)((w8.x >> 12) & 0xFFFu);
                 bb.maxx = bb.minx + 1 + (int)((w8.x >> 24) & 7u); bb.maxy = bb.miny + 1 + (int)((w8.x >> 27) & 7u);
@@ -719,7 +719,8 @@ __global__ __launch_bounds__(256) void gut_tile_ranges_kernel(uint32_t n_cap, co
 // ---------------------------------------------------------------------------------------------
 // K9: gradient finalisation = per-particle gather of the compositing partials + projection backward
 // (GUTProjector::evalBackward, gutProjector.cuh:390-430).  One lane per particle:
-//   * sums the particle's slots [2 off, 2 (off + count)) that the gradient sweep flagged (particles covering many
+//   * sums the particle's slots [2 off, 2 (off + count)) that the gradient sweep marked as written - GutGradSlots: the particle's word
+//     for its first 64 slots, a byte per slot beyond - and stores 0 over every mark it found set (particles covering many
 //     tiles are gathered by the whole wave instead, so that no lane becomes the critical path);
 //   * contracts (B, M) into the position / quaternion / scale gradients (matmul_bw_vec, matmul_bw_quat and the
 //     1/scale chain of models/gaussianParticles.cuh:624-751, applied once per particle instead of once per hit);
@@ -733,9 +734,6 @@ __global__ __launch_bounds__(256) void gut_tile_ranges_kernel(uint32_t n_cap, co
 // its largest particle (mean 17 tiles, p99 84, max 743 on the bench cloud: 23 % efficiency if every quad gathers alone);
 // gather + projection backward at thresholds 128 / 64 / 32 / 16: 0.262 / 0.241 / 0.227 / 0.227 ms
 constexpr uint32_t kGatherSmall = 32;
-struct __attribute__((packed, aligned(2))) FlagChunk {
-    unsigned long long lo, hi;
-};
 
 // gradient of sum_ij m_ij rotT_ij(q) w.r.t. q = (r,x,y,z); q2 = 2q (matmul_bw_quat, mathUtils.cuh:458-521)
 __device__ __forceinline__ float4 quat_contract(const float m[9], float4 q2) {
@@ -815,7 +813,7 @@ __device__ __forceinline__ float xor_sum_quads(float v) {  // sum over the 16 qu
 // kernel.  The quad that gathered a particle splits its 16 SH coefficients four ways: lane c owns coefficients 4c .. 4c+3 = floats
 // [12 c, 12 c + 12) of the row, which are three consecutive 16-byte words - so the wave's 16 rows are read and their gradient rows written
 // as 3 float4 per lane at float4 index 3 lane + {0, 1, 2}, straight from / to global memory (no LDS transpose), requested at the top of the
-// kernel so that their round trip lies under the flag -> row chain.  Rows of particles without tiles are not read (a third of them) and
+// kernel so that their round trip lies under the mask -> row chain.  Rows of particles without tiles are not read (a third of them) and
 // their gradient rows are written as zeros.  Saves a launch, the g_rgb round trip, the second read of the particle rows and the
 // read-modify-write of the position gradient.
 template <int STRIDE, bool NHT = false, bool FUSE_SH = false>
@@ -830,9 +828,12 @@ __global__ __launch_bounds__(256) void gut_grad_gather_kernel(GutParams P, GutPr
     const bool has = count != 0;
     QuadAcc<STRIDE> acc;
     acc.clear();
-    const uint32_t off = has ? proj.part_offset[i] : 0u;
+    const uint32_t off = (i < end) ? proj.part_offset[i] : 0u;   // (meaningful where has; requested without waiting for the count)
+    // which of the particle's first 64 slots the sweep wrote (GutGradSlots): a coalesced load that depends on nothing, like the two
+    // above.  What is read is cleared again (below): both levels of marks are all zero between backwards
+    const unsigned long long touched = (have_partials && i < end) ? slots.touched[i] : 0ull;
     // the particle's own parameters are needed only by the closing arithmetic; requested here, their round trip overlaps the
-    // flag -> row chain below instead of following it
+    // mask -> row chain below instead of following it
     float4 q = make_float4(1.f, 0.f, 0.f, 0.f), sc = make_float4(1.f, 1.f, 1.f, 0.f);
     if (has) { q = density12[3 * (size_t)i + 1]; sc = density12[3 * (size_t)i + 2]; }
     float4 sh0 = make_float4(0.f, 0.f, 0.f, 0.f), sh1 = sh0, sh2 = sh0, pa = sh0;
@@ -845,34 +846,24 @@ __global__ __launch_bounds__(256) void gut_grad_gather_kernel(GutParams P, GutPr
     }
     if (have_partials) {
         if (has && count <= kGatherSmall) {
-            // Set flags are rare (most tile entries lie behind the rays' termination) and every load here is a dependent
-            // round trip to HBM, so requests are issued in groups: 64 flags (four 16-byte loads) are packed into one bit
-            // mask, then the rows of up to four set bits are requested together before any of them is summed.
-            const size_t s0 = 2 * (size_t)off;
+            // Set marks are rare (most tile entries lie behind the rays' termination) and every row is a round trip to HBM, so
+            // requests are issued in groups: the rows of up to four set bits are requested together before any of them is summed.
+            // All 2 count <= 64 slots of the particle are bits of its word (masked to them: the sweep sets no others).
+            static_assert(2 * kGatherSmall <= kGutTouchBits, "the quad path reads its marks from the particle's word alone");
+            const size_t sb = 2 * (size_t)off;
             const uint32_t nb = 2 * count;
-            for (uint32_t base = 0; base < nb; base += 64) {
-                const FlagChunk* fc = reinterpret_cast<const FlagChunk*>(slots.flag + s0 + base);  // buffer has 96 B of slack
-                const FlagChunk w0 = fc[0], w1 = fc[1], w2 = fc[2], w3 = fc[3];
-                // gather bit 0 of each of 8 flag bytes into one byte (bytes past the flag array are arbitrary: keep bit 0 only,
-                // or they would carry into their neighbours' bits)
-                constexpr unsigned long long kPack = 0x0102040810204080ull, kLsb = 0x0101010101010101ull;
-                auto pack8 = [](unsigned long long w) { return ((w & kLsb) * kPack) >> 56; };
-                unsigned long long m = pack8(w0.lo) | (pack8(w0.hi) << 8) | (pack8(w1.lo) << 16) | (pack8(w1.hi) << 24) |
-                                       (pack8(w2.lo) << 32) | (pack8(w2.hi) << 40) | (pack8(w3.lo) << 48) | (pack8(w3.hi) << 56);
-                const uint32_t rem = nb - base;
-                if (rem < 64) m &= (1ull << rem) - 1ull;
-                const size_t sb = s0 + base;
-                while (m) {
-                    const int b0 = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    const int b1 = m ? __ffsll((long long)m) - 1 : -1;
-                    m &= m - 1;   // m == 0 stays 0
-                    const int b2 = m ? __ffsll((long long)m) - 1 : -1;
-                    m &= m - 1;
-                    const int b3 = m ? __ffsll((long long)m) - 1 : -1;
-                    m &= m - 1;
-                    acc.add_rows4(slots.partial, sb, b0, b1, b2, b3, c);
-                }
+            unsigned long long m = touched;
+            if (nb < 64) m &= (1ull << nb) - 1ull;
+            while (m) {
+                const int b0 = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                const int b1 = m ? __ffsll((long long)m) - 1 : -1;
+                m &= m - 1;   // m == 0 stays 0
+                const int b2 = m ? __ffsll((long long)m) - 1 : -1;
+                m &= m - 1;
+                const int b3 = m ? __ffsll((long long)m) - 1 : -1;
+                m &= m - 1;
+                acc.add_rows4(slots.partial, sb, b0, b1, b2, b3, c);
             }
         }
         // the heavy tail: all 16 quads of the wave share one particle's slots
@@ -884,12 +875,20 @@ __global__ __launch_bounds__(256) void gut_grad_gather_kernel(GutParams P, GutPr
             const uint32_t n2 = 2u * (uint32_t)__builtin_amdgcn_readlane((int)count, src);
             QuadAcc<STRIDE> part;
             part.clear();
-            // 64 flags per step, one byte per lane, turned into a wave-uniform mask by a ballot; quad g owns bits g, g+16, g+32,
-            // g+48 of it and requests its set rows together
+            // 64 marks per step as a wave-uniform mask: the first step's is the particle's word (n2 > 64: all its bits are slots),
+            // the later ones a ballot over the slots' bytes, one per lane (a set byte is cleared by the lane that read it);
+            // quad g owns bits g, g+16, g+32, g+48 of the mask and requests its set rows together
             const int g = lane >> 2;
+            const unsigned long long m0 = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)touched, src) |
+                                          ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(touched >> 32), src) << 32);
+#pragma nounroll   // (nor peeled: a second copy of the body for the first step costs the kernel a wave per SIMD)
             for (uint32_t base = 0; base < n2; base += 64) {
-                const bool set = (base + (uint32_t)lane < n2) && slots.flag[s0 + base + lane] != 0;
-                const unsigned long long m = __ballot(set);
+                unsigned long long m = m0;
+                if (base > 0) {
+                    const bool set = (base + (uint32_t)lane < n2) && slots.flag[s0 + base + lane] != 0;
+                    if (set) slots.flag[s0 + base + lane] = 0;
+                    m = __ballot(set);
+                }
                 if (m == 0) continue;
                 int b[4], nb = 0;
 #pragma unroll
@@ -906,6 +905,7 @@ __global__ __launch_bounds__(256) void gut_grad_gather_kernel(GutParams P, GutPr
             }
             if ((lane >> 2) == (src >> 2)) acc = part;
         }
+        if (touched != 0ull && c == 0) slots.touched[i] = 0ull;
     }
     // every lane of the quad collects the whole row sum (column j from lane j) and redoes the small closing arithmetic;
     // lane c then stores output column c, so a particle's 48 + 12 bytes leave as neighbouring requests

@@ -364,7 +364,7 @@ __device__ __forceinline__ void render_bwd_sweep(const GutParams& P, const RayPa
                                                  uint32_t half, const EntryLists& lists, const float4* __restrict__ density12,
                                                  const float* __restrict__ rgb, const GutGradSlots& slots,
                                                  float4* __restrict__ s_rec, float* __restrict__ s_acc, float* __restrict__ s_acc2,
-                                                 float* __restrict__ s_tr, const BwdPixels& px) {
+                                                 float* __restrict__ s_tr, uint2* __restrict__ s_who, const BwdPixels& px) {
     constexpr uint32_t kBatch = kBwdBatch;
     v2f T = px.T, D = px.D, Cr = px.Cr, Cg = px.Cg, Cb = px.Cb;
     const v2f T_fin = px.T_fin, D_fin = px.D_fin, gT = px.gT, gD = px.gD;
@@ -377,7 +377,11 @@ __device__ __forceinline__ void render_bwd_sweep(const GutParams& P, const RayPa
     while (b < seg_end) {
         if (!__any(alive0 || alive1)) break;
         const uint32_t bend = min(seg_end, (b & ~(kBatch - 1u)) + kBatch);
-        if (lane < (int)kBatch) stage_entry<DEG, true>(P, next, UNI, rp.origin, &s_rec[lane * kRecQuads]);
+        if (lane < (int)kBatch) {
+            stage_entry<DEG, true>(P, next, UNI, rp.origin, &s_rec[lane * kRecQuads]);
+            // the flush marks the entry's slot under its particle and ordinal: parked here, `next` is about to be overwritten
+            s_who[lane] = make_uint2(next.idx, entry_ordinal(next, lists, slots.part_offset));
+        }
         __syncthreads();
         next = load_entry(bend + lane, min(seg_end, bend + kBatch), lists, density12, rgb);
         const int n = (int)(bend - b);
@@ -530,7 +534,8 @@ __device__ __forceinline__ void render_bwd_sweep(const GutParams& P, const RayPa
             float4* out = reinterpret_cast<float4*>(slots.partial + slot * (HAS_GDIST ? 20 : 16));
             out[0] = a0; out[1] = a1; out[2] = a2; out[3] = a3;
             if (HAS_GDIST) out[4] = make_float4(s_acc2[lane * 16], s_acc2[lane * 16 + 1], s_acc2[lane * 16 + 2], 0.f);
-            slots.flag[slot] = 1;
+            const uint2 who = s_who[lane];
+            mark_slot(slots, who.x, who.y, half, slot);
         }
         __syncthreads();
         b = bend;
@@ -555,6 +560,7 @@ __global__ __launch_bounds__(64) void gut_render_bwd_kernel(
     __shared__ float s_tr[16 * 65];                            // transposition buffer of the per-entry reduction
     __shared__ float s_acc[kBatch * 16];                       // per staged entry: the wave totals of its 16 terms
     __shared__ float s_acc2[HAS_GDIST ? kBatch * 16 : 1];      // depth-gradient extras (3 terms used)
+    __shared__ uint2 s_who[kBatch];                            // per staged entry: {particle, ordinal among the particle's tile entries}
     // task = (virtual tile, half).  Virtual tiles [0, bndPad) are the segments that start at segment boundary b (sorted
     // index b * kGutSegment): they are the long, dense tasks and are dispatched first so that the tail of the launch
     // is made of the short first segments of each tile list, virtual tiles [bndPad, bndPad + tiles).  Only a quarter of the
@@ -620,9 +626,9 @@ __global__ __launch_bounds__(64) void gut_render_bwd_kernel(
 
     BwdPixels px{T, D, Cr, Cg, Cb, T_fin, D_fin, gT, gD, C_fin, gC, alive0, alive1};
     if (rp.uniform_origin)
-        render_bwd_sweep<DEG, HAS_GDIST, true, COUNT>(P, rp, seg_begin, seg_end, lane, half, lists, density12, rgb, slots, s_rec, s_acc, s_acc2, s_tr, px);
+        render_bwd_sweep<DEG, HAS_GDIST, true, COUNT>(P, rp, seg_begin, seg_end, lane, half, lists, density12, rgb, slots, s_rec, s_acc, s_acc2, s_tr, s_who, px);
     else
-        render_bwd_sweep<DEG, HAS_GDIST, false, COUNT>(P, rp, seg_begin, seg_end, lane, half, lists, density12, rgb, slots, s_rec, s_acc, s_acc2, s_tr, px);
+        render_bwd_sweep<DEG, HAS_GDIST, false, COUNT>(P, rp, seg_begin, seg_end, lane, half, lists, density12, rgb, slots, s_rec, s_acc, s_acc2, s_tr, s_who, px);
     if (COUNT && P.work && lane == 0) {   // diagnostics (after the forward sweep's block of per-wave words): lifetime and start of this task
         const size_t gid = (size_t)atomicAdd(&P.work[8], 1ull);
         const size_t base = 16 + 4 * (size_t)(((num_tiles + 7u) & ~7u) * 2u) + 2 * gid;

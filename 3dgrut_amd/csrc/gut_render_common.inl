@@ -184,6 +184,18 @@ __device__ __forceinline__ RawEntry load_entry(uint32_t e, uint32_t end, const E
     }
     return r;
 }
+// a loaded entry's ordinal among its particle's tile entries (gradient sweeps: GutGradSlots); padding = 0
+__device__ __forceinline__ uint32_t entry_ordinal(const RawEntry& r, const EntryLists& lists, const uint32_t* __restrict__ part_offset) {
+    if (r.idx == 0xFFFFFFFFu) return 0u;
+    return r.pos - (lists.rec64 ? __float_as_uint(r.s.w) : part_offset[r.idx]);
+}
+// mark a written gradient slot: one bit of the particle's word for its first 32 tile entries (set by waves anywhere on the device:
+// a return-less atomic OR), the slot's byte beyond
+__device__ __forceinline__ void mark_slot(const GutGradSlots& slots, uint32_t particle, uint32_t ordinal, uint32_t half, size_t slot) {
+    const uint32_t bit = 2u * ordinal + half;
+    if (bit < kGutTouchBits) atomicOr(&slots.touched[particle], 1ull << bit);
+    else slots.flag[slot] = 1;
+}
 template <int DEG, bool INVERSE_SCALE>
 __device__ __forceinline__ void stage_entry(const GutParams& P, const RawEntry& r, bool uniform_origin, f3 origin, float4* __restrict__ rec) {
     float4 r0 = make_float4(1.f, 0.f, 0.f, 0.f), r1 = make_float4(0.f, 1.f, 0.f, 0.f), r2 = make_float4(0.f, 0.f, 1.f, 0.f);

@@ -266,6 +266,7 @@ __device__ __forceinline__ void nht_bwd_sweep(const GutParams& P, const RayPair&
         if (lane < (int)kNhtBatch) {
             stage_entry<DEG, true>(P, next, UNI, rp.origin, &s_rec[lane * kRecQuads]);
             reinterpret_cast<uint32_t*>(&s_rec[lane * kRecQuads + 4])[0] = next.idx;   // (the radiance slot of the record is unused here)
+            reinterpret_cast<uint32_t*>(&s_rec[lane * kRecQuads + 4])[1] = entry_ordinal(next, lists, slots.part_offset);   // for the flush's mark
         }
         nht_stage_features(P, features, (uint32_t)__shfl((int)next.idx, lane >> 1, 64), lane, s_feat);
         __syncthreads();
@@ -439,7 +440,8 @@ __device__ __forceinline__ void nht_bwd_sweep(const GutParams& P, const RayPair&
             const size_t slot = 2 * (size_t)pos + half;
             float4* out = reinterpret_cast<float4*>(slots.partial + slot * 16);
             out[0] = a0; out[1] = a1; out[2] = a2; out[3] = a3;
-            slots.flag[slot] = 1;
+            const uint32_t* who = reinterpret_cast<const uint32_t*>(&rec[4]);
+            mark_slot(slots, who[0], who[1], half, slot);
         }
         __syncthreads();
         b = bend;
