@@ -418,7 +418,13 @@ __device__ __forceinline__ void render_bwd_sweep(const GutParams& P, const RayPa
 
             const v2f vu = pdot(g.v, g.u);
             const v2f t = vu * il2;
-            const p3 a = p3{pfma(-t, g.v.x, g.u.x), pfma(-t, g.v.y, g.u.y), pfma(-t, g.v.z, g.u.z)};
+            // a = u - t v as (v x u) x v / |v|^2, the reference's own form (d gray / d gro = 2 (grd x gro) x grd): the difference loses
+            // |u| / |a| in relative accuracy - |u| is the ray origin's distance in units of the particle's scales, several hundred for
+            // a thin particle, |a| < 3 on every accepted hit - and the error goes straight into B, i.e. the position gradient
+            // (1e-4 relative per hit at |u| = 490, tests/test_row_gradients_gpu.py); the cross product is already there for the
+            // accept test and is orthogonal to v, so the second product cancels nothing.  (a is left un-normalised here,
+            // a = |v|^2 (u - t v): its only use is a * wg2, and wg2 takes the 1 / |v|^2)
+            const p3 a = pcross(g.c, g.v);
             // canonical-frame offsets of the ray origin, needed un-scaled for the rotation gradient
             p3 dl;
             if (UNI) dl = p3{splat(rp.origin.x - r0.w), splat(rp.origin.y - r1.w), splat(rp.origin.z - r2.w)};
@@ -454,7 +460,7 @@ __device__ __forceinline__ void render_bwd_sweep(const GutParams& P, const RayPa
             const v2f dn = resp * dalpha;
             const v2f dresp = r3.w * dalpha;
             const v2f wg2 = psel(h0, h1, 2.f * v2f{particle_response_grd<DEG>(gray.x, resp.x, dresp.x),
-                                                    particle_response_grd<DEG>(gray.y, resp.y, dresp.y)}, splat(0.f));
+                                                    particle_response_grd<DEG>(gray.y, resp.y, dresp.y)}, splat(0.f)) * il2;
             p3 uGrd = p3{a.x * wg2, a.y * wg2, a.z * wg2};                 // d L / d gro
             float terms[16], extra[16];
             if (!HAS_GDIST) {

@@ -309,6 +309,7 @@ __device__ __forceinline__ bool pyramid_misses(const WavePyramid& w, float4 r0, 
 // canonical-frame ray of the pixel pair against one staged entry, and the accept test
 struct PairGeom {
     p3 u, v;        // canonical origin, canonical (un-normalised) direction
+    p3 c;           // v x u (the SH gradient sweep rebuilds the closest point's offset from it)
     v2f l2, cc;     // |v|^2, |v x u|^2  (grayDist = cc / l2)
     bool acc0, acc1;
 };
@@ -326,8 +327,8 @@ __device__ __forceinline__ PairGeom pair_geometry(const RayPair& rp, const float
         g.u = p3{pdot(m0, dl), pdot(m1, dl), pdot(m2, dl)};
     }
     g.l2 = pdot(g.v, g.v);
-    const p3 c = pcross(g.v, g.u);
-    g.cc = pdot(c, c);
+    g.c = pcross(g.v, g.u);
+    g.cc = pdot(g.c, g.c);
     const v2f lim = rec[4].w * g.l2;
     g.acc0 = g.cc.x < lim.x;
     g.acc1 = g.cc.y < lim.y;

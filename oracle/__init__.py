@@ -182,8 +182,12 @@ def gut_forward_nht(cfg, cam, pose_start, pose_end, density12, features, ray_o, 
     return dict(feat_density=fd, hit_distance=dist, hit_count=cnt, sorted_idx=bins["sorted_idx"], tile_ranges=bins["tile_ranges"], proj=proj)
 
 
-def gut_backward_nht(cfg, cam, pose_start, pose_end, density12, features, ray_o, ray_d, fwd, g_feat_density, g_hit_distance=None, nht=None, dtype=np.float32):
-    """Gradients of the nht forward (K = 0): (grad_density12 [N,12], grad_features [N,K])."""
+def gut_backward_nht(cfg, cam, pose_start, pose_end, density12, features, ray_o, ray_d, fwd, g_feat_density, g_hit_distance=None, nht=None, dtype=np.float32,
+                     budgets=False):
+    """Gradients of the nht forward: (grad_density12 [N,12], grad_features [N,K]).
+
+    budgets=True: additionally a dict of the float64 per-element budgets (gut_oracle.c: orc_budget) d1, dT [N,12] and f1, fT [N,K], and
+    hits [N], the number of hits differentiated per particle."""
     nht = dict(NHT_DEFAULT, **(nht or {}))
     l = lib(dtype)
     H, W = cam.height, cam.width
@@ -192,15 +196,25 @@ def gut_backward_nht(cfg, cam, pose_start, pose_end, density12, features, ray_o,
     gd, gf = np.zeros((n, 12), dtype), np.zeros((n, nht["particle_feature_dim"]), dtype)
     gdist = np.zeros((H, W, 1), dtype) if g_hit_distance is None else _c(g_hit_distance, dtype)
     ro, rd = _c(ray_o, dtype).reshape(H, W, 3), _c(ray_d, dtype).reshape(H, W, 3)
-    rc = l.orc_gut_render_nht_bwd(C.byref(cfg), _p(prm), W, H, _p(_c(pose_start, dtype)), _p(_c(pose_end, dtype)), _p(_c(density12, dtype)),
-                                  _p(_c(features, dtype)), _p(fwd["sorted_idx"]), _p(fwd["tile_ranges"]), _p(ro), _p(rd),
-                                  _p(_c(fwd["feat_density"], dtype)), _p(_c(g_feat_density, dtype)), _p(_c(fwd["hit_distance"], dtype)), _p(gdist), _p(gd), _p(gf))
+    args = (C.byref(cfg), _p(prm), W, H, _p(_c(pose_start, dtype)), _p(_c(pose_end, dtype)), _p(_c(density12, dtype)),
+            _p(_c(features, dtype)), _p(fwd["sorted_idx"]), _p(fwd["tile_ranges"]), _p(ro), _p(rd),
+            _p(_c(fwd["feat_density"], dtype)), _p(_c(g_feat_density, dtype)), _p(_c(fwd["hit_distance"], dtype)), _p(gdist), _p(gd), _p(gf))
+    if budgets:
+        bud = dict(d1=np.zeros((n, 12)), dT=np.zeros((n, 12)), f1=np.zeros(gf.shape), fT=np.zeros(gf.shape), hits=np.zeros(n))
+        assert l.orc_gut_render_nht_bwd_budget(*args, _p(bud["d1"]), _p(bud["dT"]), _p(bud["f1"]), _p(bud["fT"]), _p(bud["hits"])) == 0
+        return gd, gf, bud
+    rc = l.orc_gut_render_nht_bwd(*args)
     assert rc == 0
     return gd, gf
 
 
-def gut_backward(cfg, cam, n_active, fwd, g_feat_density, g_hit_distance, dtype=np.float32):
-    """Reference backward (SplatRaster::trace_bwd): returns (grad_density12 [N,12], grad_sph [N,3*ncoef])."""
+def gut_backward(cfg, cam, n_active, fwd, g_feat_density, g_hit_distance, dtype=np.float32, budgets=False):
+    """Reference backward (SplatRaster::trace_bwd): returns (grad_density12 [N,12], grad_sph [N,3*ncoef], grad_rgb [N,3]).
+
+    budgets=True: additionally a dict of the float64 per-element budgets (gut_oracle.c: orc_budget) B_1 = sum |c| and B_T = sum |c| / T
+    of the three gradients: d1, dT [N,12]; sph1, sphT [N,3*ncoef]; rgb1, rgbT [N,3] - the latter two carried through the projection
+    backward (orc_gut_project_bwd_budget), which also adds the direction term to the position columns of d1 / dT; and hits [N], the
+    number of hits differentiated per particle (the number of terms of each of its sums)."""
     l = lib(dtype)
     H, W = cam.height, cam.width
     d12, sph = fwd["density12"], fwd["sph"]
@@ -211,13 +225,26 @@ def gut_backward(cfg, cam, n_active, fwd, g_feat_density, g_hit_distance, dtype=
     grgb = np.zeros((N, 3), dtype)
     gsph = np.zeros_like(sph)
     gfd, gdist = _c(g_feat_density, dtype), _c(g_hit_distance, dtype)
+    bud = None
+    if budgets:
+        bud = dict(d1=np.zeros((N, 12)), dT=np.zeros((N, 12)), rgb1=np.zeros((N, 3)), rgbT=np.zeros((N, 3)),
+                   sph1=np.zeros(sph.shape), sphT=np.zeros(sph.shape), hits=np.zeros(N))
     if fwd["bins"]["num_intersections"] > 0:
-        r = l.orc_gut_render_bwd(C.byref(cfg), C.c_int(W), C.c_int(H), _p(ps), _p(pe), _p(d12), _p(fwd["proj"]["rgb"]),
-                                 _p(fwd["bins"]["sorted_idx"]), _p(fwd["bins"]["tile_ranges"]), _p(ro), _p(rd),
-                                 _p(fwd["feat_density"]), _p(gfd), _p(fwd["hit_distance"]), _p(gdist), _p(gd), _p(grgb))
+        args = (C.byref(cfg), C.c_int(W), C.c_int(H), _p(ps), _p(pe), _p(d12), _p(_c(fwd["proj"]["rgb"], dtype)),
+                _p(fwd["bins"]["sorted_idx"]), _p(fwd["bins"]["tile_ranges"]), _p(ro), _p(rd),
+                _p(_c(fwd["feat_density"], dtype)), _p(gfd), _p(_c(fwd["hit_distance"], dtype)), _p(gdist), _p(gd), _p(grgb))
+        if budgets:
+            r = l.orc_gut_render_bwd_budget(*args, _p(bud["d1"]), _p(bud["dT"]), _p(bud["rgb1"]), _p(bud["rgbT"]), _p(bud["hits"]))
+        else:
+            r = l.orc_gut_render_bwd(*args)
         assert r == 0
-    l.orc_gut_project_bwd(C.byref(cfg), _p(ps), _p(pe), C.c_uint32(N), C.c_int(n_active),
-                          _p(fwd["proj"]["tiles_count"]), _p(d12), _p(sph), _p(grgb), _p(gd), _p(gsph))
+    tc = np.ascontiguousarray(fwd["proj"]["tiles_count"], np.uint32)
+    l.orc_gut_project_bwd(C.byref(cfg), _p(ps), _p(pe), C.c_uint32(N), C.c_int(n_active), _p(tc), _p(d12), _p(sph), _p(grgb), _p(gd), _p(gsph))
+    if budgets:
+        for k in ("1", "T"):
+            l.orc_gut_project_bwd_budget(C.byref(cfg), _p(ps), _p(pe), C.c_uint32(N), C.c_int(n_active), _p(tc), _p(d12), _p(sph),
+                                         _p(bud["rgb" + k]), _p(bud["d" + k]), _p(bud["sph" + k]))
+        return gd, gsph, grgb, bud
     return gd, gsph, grgb
 
 

@@ -927,9 +927,33 @@ int orc_gut_pixel_trace_nht(const GutConfig* cfg, const int* nht, int width, int
     return (int)n;
 }
 
+/* --------------------------------------------------------------------------------------
+ * per-row error budgets of the backward sums (tests/row_budget.py): next to a gradient element g = sum over hits of c, the two
+ * non-negative sums  B_1 = sum |c|  and  B_T = sum |c| / T,  T = the ray's transmittance immediately before that hit is blended.
+ * A hit's gradient rebuilds the residual radiance / distance as (final - running) / nextT, so its rounding error scales with 1 / T
+ * and not with its own size: eps B_T is the bound that holds row by row, eps B_1 the one of the summation alone.
+ * Optional (all pointers NULL = off: the gradient entry points below are unchanged); float64 in both builds.
+ * d1, dT [N,12] like g_density12; c1, cT like the second gradient (per-particle radiance [N,3], feature rows [N,K]);
+ * hits [N] (may be NULL): the number of hits differentiated per particle - the number of terms of each of its sums. */
+typedef struct { double* d1; double* dT; double* c1; double* cT; double* hits; } orc_budget;
+static void budget_hit(const orc_budget* bud, size_t idx) {
+    if (!bud || !bud->hits) return;
+#pragma omp atomic
+    bud->hits[idx] += 1;
+}
+static void budget_add(double* b1, double* bT, size_t i, real c, real T) {
+    const double a = fabs((double)c);
+    if (a == 0) return;
+    const double at = a / (double)T;
+#pragma omp atomic
+    b1[i] += a;
+#pragma omp atomic
+    bT[i] += at;
+}
+
 static size_t list_particle_bound(int width, int height, const uint32_t* sorted_idx, const uint32_t* tile_ranges);
 typedef struct {
-    const GutConfig* cfg; const int* nht; const real* density12; const real* features; double* acc_d; double* acc_f;
+    const GutConfig* cfg; const int* nht; const real* density12; const real* features; double* acc_d; double* acc_f; const orc_budget* bud;
     v3 v0, e1, e2, e3, c23, gw[4]; real inv_det; int nr, K, ipd, act, nf, points;
 } nht_bwd_ctx;
 typedef struct { real Cb[ORC_NHT_MAX_RAY_DIM], gC[ORC_NHT_MAX_RAY_DIM], Tb, gT, Db, gD, T; int alive; } nht_bwd_ray;
@@ -1015,6 +1039,7 @@ static void nht_bwd_hit(const nht_bwd_ctx* c, const orc_ray* rayp, nht_bwd_ray* 
             if (g != 0) {
 #pragma omp atomic
                 acc_f[(size_t)K * idx + k * ipd + n] += (double)g;
+                if (c->bud) budget_add(c->bud->c1, c->bud->cT, (size_t)K * idx + k * ipd + n, g, st->T);
             }
             dwk += row[k * ipd + n] * gbase[n];
         }
@@ -1061,7 +1086,9 @@ static void nht_bwd_hit(const nht_bwd_ctx* c, const orc_ray* rayp, nht_bwd_ray* 
         if (gd[k] != 0) {
 #pragma omp atomic
             acc_d[12 * (size_t)idx + k] += (double)gd[k];
+            if (c->bud) budget_add(c->bud->d1, c->bud->dT, 12 * (size_t)idx + k, gd[k], st->T);
         }
+    budget_hit(c->bud, idx);
     st->Tb = Tb; st->gT = gT; st->Db = Db; st->gD = gD;
     st->T *= (1 - alpha);
     if (st->T < (real)cfg->min_transmittance) st->alive = 0;
@@ -1074,10 +1101,10 @@ static void nht_bwd_hit(const nht_bwd_ctx* c, const orc_ray* rayp, nht_bwd_ray* 
  * products that are not in the checkout: like process_hit_bwd_k this is the reverse mode of the restated forward, checked against
  * float64 torch.autograd of that forward (tests/golden/autograd_gut_nht.npz, make_autograd_golden.py --nht).
  * fd [H,W,nr+1] = forward results, g_fd their upstream gradients; g_density12 [N,12] and g_features [N,K] are ADDED to. */
-int orc_gut_render_nht_bwd(const GutConfig* cfg, const int* nht, int width, int height, const real* pose_start7, const real* pose_end7,
-                           const real* density12, const real* features, const uint32_t* sorted_idx, const uint32_t* tile_ranges,
-                           const real* ray_o, const real* ray_d, const real* fd, const real* g_fd, const real* dist, const real* g_dist,
-                           real* g_density12, real* g_features) {
+static int render_nht_bwd_impl(const GutConfig* cfg, const int* nht, int width, int height, const real* pose_start7, const real* pose_end7,
+                               const real* density12, const real* features, const uint32_t* sorted_idx, const uint32_t* tile_ranges,
+                               const real* ray_o, const real* ray_d, const real* fd, const real* g_fd, const real* dist, const real* g_dist,
+                               real* g_density12, real* g_features, const orc_budget* bud) {
     const orc_frame_poses fp = frame_poses(pose_start7, pose_end7);
     const int gx = tile_grid_dim(width);
     const int nr = nht_ray_dim(nht), K = nht[0], ipd = nht[1], act = nht[3], nf = nht[4];
@@ -1099,7 +1126,7 @@ int orc_gut_render_nht_bwd(const GutConfig* cfg, const int* nht, int width, int 
     gw[1] = v3_scale(c23, inv_det); gw[2] = v3_scale(v3_cross(e3, e1), inv_det); gw[3] = v3_scale(v3_cross(e1, e2), inv_det);
     gw[0] = v3_scale(v3_add(v3_add(gw[1], gw[2]), gw[3]), -1);
     nht_bwd_ctx ctx;
-    ctx.cfg = cfg; ctx.nht = nht; ctx.density12 = density12; ctx.features = features; ctx.acc_d = acc_d; ctx.acc_f = acc_f;
+    ctx.cfg = cfg; ctx.nht = nht; ctx.density12 = density12; ctx.features = features; ctx.acc_d = acc_d; ctx.acc_f = acc_f; ctx.bud = bud;
     ctx.v0 = v0; ctx.e1 = e1; ctx.e2 = e2; ctx.e3 = e3; ctx.c23 = c23; for (int k = 0; k < 4; ++k) ctx.gw[k] = gw[k];
     ctx.inv_det = inv_det; ctx.nr = nr; ctx.K = K; ctx.ipd = ipd; ctx.act = act; ctx.nf = nf; ctx.points = points;
 #pragma omp parallel for schedule(dynamic, 16)
@@ -1141,6 +1168,22 @@ int orc_gut_render_nht_bwd(const GutConfig* cfg, const int* nht, int width, int 
     for (size_t k = 0; k < n_acc * (size_t)K; ++k) g_features[k] += (real)acc_f[k];
     free(acc_d); free(acc_f);
     return 0;
+}
+int orc_gut_render_nht_bwd(const GutConfig* cfg, const int* nht, int width, int height, const real* pose_start7, const real* pose_end7,
+                           const real* density12, const real* features, const uint32_t* sorted_idx, const uint32_t* tile_ranges,
+                           const real* ray_o, const real* ray_d, const real* fd, const real* g_fd, const real* dist, const real* g_dist,
+                           real* g_density12, real* g_features) {
+    return render_nht_bwd_impl(cfg, nht, width, height, pose_start7, pose_end7, density12, features, sorted_idx, tile_ranges, ray_o, ray_d, fd, g_fd,
+                               dist, g_dist, g_density12, g_features, NULL);
+}
+/* ... with the budgets of both gradients (b1_f, bT_f [N,K]); they are ADDED to like the gradients */
+int orc_gut_render_nht_bwd_budget(const GutConfig* cfg, const int* nht, int width, int height, const real* pose_start7, const real* pose_end7,
+                                  const real* density12, const real* features, const uint32_t* sorted_idx, const uint32_t* tile_ranges,
+                                  const real* ray_o, const real* ray_d, const real* fd, const real* g_fd, const real* dist, const real* g_dist,
+                                  real* g_density12, real* g_features, double* b1_d, double* bT_d, double* b1_f, double* bT_f, double* hits) {
+    const orc_budget bud = {b1_d, bT_d, b1_f, bT_f, hits};
+    return render_nht_bwd_impl(cfg, nht, width, height, pose_start7, pose_end7, density12, features, sorted_idx, tile_ranges, ray_o, ray_d, fd, g_fd,
+                               dist, g_dist, g_density12, g_features, &bud);
 }
 
 /* Analysis aid (scripts/slab_analysis.py): per pixel, how many entries of its tile list the K = 0 forward loop examines
@@ -1274,7 +1317,7 @@ static size_t list_particle_bound(int width, int height, const uint32_t* sorted_
 static int render_bwd_kbuffer(const GutConfig* cfg, int width, int height, const real* pose_start7, const real* pose_end7,
                               const real* density12, const real* rgb, const uint32_t* sorted_idx, const uint32_t* tile_ranges,
                               const real* ray_o, const real* ray_d, const real* fd, const real* g_fd, const real* dist, const real* g_dist,
-                              real* g_density12, real* g_rgb) {
+                              real* g_density12, real* g_rgb, const orc_budget* bud) {
     const orc_frame_poses fp = frame_poses(pose_start7, pose_end7);
     const int gx = tile_grid_dim(width);
     const int K = cfg->k_buffer_size;
@@ -1306,6 +1349,11 @@ static int render_bwd_kbuffer(const GutConfig* cfg, int width, int height, const
             process_hit_bwd_k(cfg, ray.o, ray.d, &pp, v3_make(r_max(c[0], 0), r_max(c[1], 0), r_max(c[2], 0)), (h).alpha, (h).hitT, &r, gd, gf); \
             for (int k = 0; k < 11; ++k) if (gd[k] != 0) { _Pragma("omp atomic") acc_d[12 * (size_t)(h).idx + k] += (double)gd[k]; }           \
             for (int k = 0; k < 3; ++k) if (gf[k] != 0) { _Pragma("omp atomic") acc_c[3 * (size_t)(h).idx + k] += (double)gf[k]; }             \
+            if (bud) {   /* T: the transmittance in front of this hit */                                                    \
+                for (int k = 0; k < 11; ++k) budget_add(bud->d1, bud->dT, 12 * (size_t)(h).idx + k, gd[k], T);              \
+                for (int k = 0; k < 3; ++k) budget_add(bud->c1, bud->cT, 3 * (size_t)(h).idx + k, gf[k], T);                \
+                budget_hit(bud, (h).idx);                                                                                   \
+            }                                                                                                               \
             T *= (1 - (h).alpha);                                                                                           \
             if (T < (real)cfg->min_transmittance) alive = 0;                                                                \
         } while (0)
@@ -1333,14 +1381,14 @@ static int render_bwd_kbuffer(const GutConfig* cfg, int width, int height, const
     return 0;
 }
 
-int orc_gut_render_bwd(const GutConfig* cfg, int width, int height, const real* pose_start7, const real* pose_end7,
-                       const real* density12, const real* rgb, const uint32_t* sorted_idx, const uint32_t* tile_ranges,
-                       const real* ray_o, const real* ray_d,
-                       const real* fd, const real* g_fd, const real* dist, const real* g_dist,
-                       real* g_density12, real* g_rgb) {
+static int render_bwd_impl(const GutConfig* cfg, int width, int height, const real* pose_start7, const real* pose_end7,
+                           const real* density12, const real* rgb, const uint32_t* sorted_idx, const uint32_t* tile_ranges,
+                           const real* ray_o, const real* ray_d,
+                           const real* fd, const real* g_fd, const real* dist, const real* g_dist,
+                           real* g_density12, real* g_rgb, const orc_budget* bud) {
     if (cfg->k_buffer_size != 0)
         return render_bwd_kbuffer(cfg, width, height, pose_start7, pose_end7, density12, rgb, sorted_idx, tile_ranges, ray_o, ray_d, fd, g_fd, dist,
-                                  g_dist, g_density12, g_rgb);
+                                  g_dist, g_density12, g_rgb, bud);
     const orc_frame_poses fp = frame_poses(pose_start7, pose_end7);
     const int gx = tile_grid_dim(width);
     /* Per-hit gradients are computed in `real` (the reference's arithmetic type) but SUMMED in double: the reference adds them
@@ -1369,7 +1417,13 @@ int orc_gut_render_bwd(const GutConfig* cfg, int width, int height, const real* 
             const orc_particle p = load_particle(density12 + 12 * (size_t)idx);
             const real* c = rgb + 3 * (size_t)idx;
             real gd[12] = {0}, gf[3] = {0};
+            const real T_before = r.T;
             process_hit_bwd(cfg, ray.o, ray.d, &p, v3_make(r_max(c[0], 0), r_max(c[1], 0), r_max(c[2], 0)), &r, gd, gf);
+            if (bud) {
+                for (int k = 0; k < 11; ++k) budget_add(bud->d1, bud->dT, 12 * (size_t)idx + k, gd[k], T_before);
+                for (int k = 0; k < 3; ++k) budget_add(bud->c1, bud->cT, 3 * (size_t)idx + k, gf[k], T_before);
+                if (r.T != T_before) budget_hit(bud, idx);   /* accepted: alpha > min_alpha > 0 */
+            }
             for (int k = 0; k < 11; ++k) {
                 if (gd[k] != 0) {
 #pragma omp atomic
@@ -1389,6 +1443,24 @@ int orc_gut_render_bwd(const GutConfig* cfg, int width, int height, const real* 
     for (size_t k = 0; k < n_acc * 3; ++k) g_rgb[k] += (real)acc_c[k];
     free(acc_d); free(acc_c);
     return 0;
+}
+int orc_gut_render_bwd(const GutConfig* cfg, int width, int height, const real* pose_start7, const real* pose_end7,
+                       const real* density12, const real* rgb, const uint32_t* sorted_idx, const uint32_t* tile_ranges,
+                       const real* ray_o, const real* ray_d,
+                       const real* fd, const real* g_fd, const real* dist, const real* g_dist,
+                       real* g_density12, real* g_rgb) {
+    return render_bwd_impl(cfg, width, height, pose_start7, pose_end7, density12, rgb, sorted_idx, tile_ranges, ray_o, ray_d, fd, g_fd, dist, g_dist,
+                           g_density12, g_rgb, NULL);
+}
+/* ... with the budgets of both gradients, K = 0 and K > 0 (b1_d, bT_d [N,12]; b1_rgb, bT_rgb [N,3]; hits [N] or NULL; ADDED to like the gradients) */
+int orc_gut_render_bwd_budget(const GutConfig* cfg, int width, int height, const real* pose_start7, const real* pose_end7,
+                              const real* density12, const real* rgb, const uint32_t* sorted_idx, const uint32_t* tile_ranges,
+                              const real* ray_o, const real* ray_d,
+                              const real* fd, const real* g_fd, const real* dist, const real* g_dist,
+                              real* g_density12, real* g_rgb, double* b1_d, double* bT_d, double* b1_rgb, double* bT_rgb, double* hits) {
+    const orc_budget bud = {b1_d, bT_d, b1_rgb, bT_rgb, hits};
+    return render_bwd_impl(cfg, width, height, pose_start7, pose_end7, density12, rgb, sorted_idx, tile_ranges, ray_o, ray_d, fd, g_fd, dist, g_dist,
+                           g_density12, g_rgb, &bud);
 }
 
 /* --------------------------------------------------------------------------------------
@@ -1429,6 +1501,44 @@ int orc_gut_project_bwd(const GutConfig* cfg, const real* pose_start7, const rea
         const real ng = v3_dot(dir, gdir);
         const v3 gpos = v3_scale(v3_sub(gdir, v3_scale(dir, ng)), 1 / len);
         g_density12[12 * (size_t)i] += gpos.x; g_density12[12 * (size_t)i + 1] += gpos.y; g_density12[12 * (size_t)i + 2] += gpos.z;
+    }
+    return 0;
+}
+
+/* The budgets of orc_gut_render_bwd_budget carried through orc_gut_project_bwd (call once for B_1, once for B_T):
+ * SH rows  |b_k| B(g_rgb)_c  behind the same clamp gate as the gradient; position: the magnitude of the direction term is ADDED to
+ * all three components,  sum_k |db_k| sum_c B(g_rgb)_c |coeff_kc| / len  (|I - n n^T| <= 1, so it bounds each component).
+ * b_sph [N,3*ncoef] is overwritten, b_density12 [N,12] accumulated, like the gradients. */
+int orc_gut_project_bwd_budget(const GutConfig* cfg, const real* pose_start7, const real* pose_end7, uint32_t N, int n_active_features,
+                               const uint32_t* tiles_count, const real* density12, const real* sph, const double* b_rgb,
+                               double* b_density12, double* b_sph) {
+    const orc_frame_poses fp = frame_poses(pose_start7, pose_end7);
+    const int ncoef = (cfg->particle_radiance_sph_degree + 1) * (cfg->particle_radiance_sph_degree + 1);
+    const int nact = (n_active_features + 1) * (n_active_features + 1);
+    for (uint32_t i = 0; i < N; ++i) {
+        double* bs = b_sph + (size_t)i * 3 * ncoef;
+        for (int k = 0; k < 3 * ncoef; ++k) bs[k] = 0;
+        if (tiles_count[i] == 0) continue;
+        const real* pd = density12 + 12 * (size_t)i;
+        const v3 v = v3_sub(v3_make(pd[0], pd[1], pd[2]), fp.sensor_world_pos);
+        const real len = r_sqrt(v3_dot(v, v));
+        const v3 dir = v3_scale(v, 1 / len);
+        const real* coeffs = sph + (size_t)i * 3 * ncoef;
+        const v3 cu = sh_radiance_unclamped(n_active_features, coeffs, dir);
+        double g[3] = {b_rgb[3 * i], b_rgb[3 * i + 1], b_rgb[3 * i + 2]};
+        if (!(cu.x > 0)) g[0] = 0;
+        if (!(cu.y > 0)) g[1] = 0;
+        if (!(cu.z > 0)) g[2] = 0;
+        real b[16]; v3 db[16];
+        sh_basis(n_active_features, dir, b);
+        sh_basis_grad(n_active_features, dir, db);
+        double bdir = 0;
+        for (int k = 0; k < nact && k < ncoef; ++k) {
+            for (int c = 0; c < 3; ++c) bs[3 * k + c] = fabs((double)b[k]) * g[c];
+            const double s = g[0] * fabs((double)coeffs[3 * k]) + g[1] * fabs((double)coeffs[3 * k + 1]) + g[2] * fabs((double)coeffs[3 * k + 2]);
+            bdir += sqrt((double)v3_dot(db[k], db[k])) * s;
+        }
+        for (int c = 0; c < 3; ++c) b_density12[12 * (size_t)i + c] += bdir / (double)len;
     }
     return 0;
 }
