@@ -145,6 +145,7 @@ class GutGradIO(C.Structure):
                 ("grad_rotation", C.c_void_p), ("grad_scale", C.c_void_p)]
 
 MLP_ACT_NONE, MLP_ACT_RELU, MLP_ACT_SIGMOID = range(3)
+PPISP_CONTROLLER_SAVED = 1984   # GRUT_PPISP_CONTROLLER_SAVED: 1600 pooled features + 3 x 128 trunk activations
 
 
 class GrutMlpConfig(C.Structure):
@@ -173,6 +174,7 @@ EXPORTED_SYMBOLS = [
     "grut_photo_loss_forward", "grut_photo_loss_backward", "grut_photo_loss_partials",
     "grut_knn", "grut_knn_scratch_bytes",
     "grut_ppisp_forward", "grut_ppisp_backward", "grut_ppisp_partials",
+    "grut_ppisp_controller_forward", "grut_ppisp_controller_backward", "grut_ppisp_controller_forward_scratch", "grut_ppisp_controller_backward_scratch",
     "grut_mlp_forward", "grut_mlp_lds_bytes", "grut_mlp_num_params",
     "grut_mlp_backward", "grut_mlp_backward_lds_bytes", "grut_mlp_backward_scratch_bytes",
     "grut_decode_forward", "grut_decode_backward",
@@ -329,6 +331,15 @@ def _declare(lib):
     lib.grut_ppisp_backward.restype = C.c_int
     lib.grut_ppisp_partials.argtypes = [C.c_uint32]
     lib.grut_ppisp_partials.restype = C.c_uint32
+    # stream, h, w, hdr, prior (device, may be NULL), weights (host array of 16 device pointers), then scratch, saved (may be NULL), out[9]
+    # / saved, grad_out[9], scratch, grads (host array of 16 device pointers)
+    lib.grut_ppisp_controller_forward.argtypes = [vp, C.c_int, C.c_int, fp, fp, C.POINTER(C.c_void_p), fp, fp, fp]
+    lib.grut_ppisp_controller_forward.restype = C.c_int
+    lib.grut_ppisp_controller_backward.argtypes = [vp, C.c_int, C.c_int, fp, fp, C.POINTER(C.c_void_p), fp, fp, fp, C.POINTER(C.c_void_p)]
+    lib.grut_ppisp_controller_backward.restype = C.c_int
+    for fn in (lib.grut_ppisp_controller_forward_scratch, lib.grut_ppisp_controller_backward_scratch):
+        fn.argtypes = [C.c_int, C.c_int]
+        fn.restype = C.c_uint64
     # stream, config, params, input [P, F + 3], num_pixels, out [P, n_output_dims]
     lib.grut_mlp_forward.argtypes = [vp, C.POINTER(GrutMlpConfig), fp, fp, C.c_uint32, fp]
     lib.grut_mlp_forward.restype = C.c_int

@@ -36,7 +36,8 @@ _LATENT_MAPS = (((0.0480542, -0.0043631), (-0.0043631, 0.0481283)),     # blue
                 ((0.0580570, -0.0179872), (-0.0179872, 0.0431061)),     # red
                 ((0.0433336, -0.0180537), (-0.0180537, 0.0580500)),     # green
                 ((0.0128369, -0.0034654), (-0.0034654, 0.0128158)))     # neutral
-stats = {"forward_calls": 0, "backward_calls": 0, "torch_calls": 0}   # which path ran (tests); plain counters
+stats = {"forward_calls": 0, "backward_calls": 0, "torch_calls": 0,   # which path ran (tests); plain counters
+         "controller_hip_calls": 0, "controller_torch_calls": 0, "controller_hip_backward_calls": 0}
 
 
 # ---- the model in torch: the path of everything that is not an fp32 CUDA tensor, and the benchmark's baseline ------------------------------
@@ -207,6 +208,58 @@ class PPISPConfig:
     final_lr_factor: float = 0.01
 
 
+_fused_controller = False
+
+
+def install_fused_controller(enable: bool = True) -> bool:
+    """Switch the controllers' fp32 CUDA forward (and their weight gradients) to csrc/ppisp_controller.hip.  Off by default; returns the
+    previous state.  Inputs the kernels do not take keep running the torch code (see _PPISPController.forward)."""
+    global _fused_controller
+    previous, _fused_controller = _fused_controller, bool(enable)
+    return previous
+
+
+class _ControllerApply(torch.autograd.Function):
+    """hdr [H, W, 3], prior [1] (neither differentiable), keep (a backward may follow: the forward writes what it needs) and the sixteen
+    parameters in the order of the C entry point -> [9]: the exposure, then the colour latents."""
+
+    @staticmethod
+    def forward(ctx, hdr, prior, keep, *params):
+        lib = _abi.load_library()
+        h, w = int(hdr.shape[0]), int(hdr.shape[1])
+        dev = hdr.device
+        out = torch.empty(9, dtype=torch.float32, device=dev)
+        saved = torch.empty(_abi.PPISP_CONTROLLER_SAVED, dtype=torch.float32, device=dev) if keep else None
+        scratch = torch.empty(int(lib.grut_ppisp_controller_forward_scratch(h, w)), dtype=torch.float32, device=dev)
+        weights = (C.c_void_p * 16)(*[p.data_ptr() for p in params])   # read live at every launch: nothing of the weights is cached
+        stats["controller_hip_calls"] += 1
+        with torch.cuda.device(dev):
+            _abi.check(lib.grut_ppisp_controller_forward(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), h, w, _row_ptr(hdr, 0),
+                                                         _row_ptr(prior, 0), weights, _row_ptr(scratch, 0), _row_ptr(saved, 0), _row_ptr(out, 0)),
+                       "grut_ppisp_controller_forward")
+        if saved is not None:
+            ctx.save_for_backward(hdr, prior, saved, *params)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        hdr, prior, saved, *params = ctx.saved_tensors
+        lib = _abi.load_library()
+        h, w = int(hdr.shape[0]), int(hdr.shape[1])
+        dev = hdr.device
+        grad_out = grad_out.to(torch.float32).contiguous()
+        grads = [torch.empty_like(p) for p in params]   # the library writes every tensor completely
+        scratch = torch.empty(int(lib.grut_ppisp_controller_backward_scratch(h, w)), dtype=torch.float32, device=dev)
+        stats["controller_hip_backward_calls"] += 1
+        with torch.cuda.device(dev):
+            _abi.check(lib.grut_ppisp_controller_backward(
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), h, w, _row_ptr(hdr, 0), _row_ptr(prior, 0),
+                (C.c_void_p * 16)(*[p.data_ptr() for p in params]), _row_ptr(saved, 0), _row_ptr(grad_out, 0), _row_ptr(scratch, 0),
+                (C.c_void_p * 16)(*[g.data_ptr() for g in grads])), "grut_ppisp_controller_backward")
+        return (None, None, None, *(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])))
+
+
 class _PPISPController(nn.Module):
     """Per-camera predictor of a frame's exposure and colour latents from the rendered image: the architecture the reference's exporter
     checks (export/usd/post_processing/ppisp_controller_weights.py).  The heads start at zero: no correction."""
@@ -222,8 +275,26 @@ class _PPISPController(nn.Module):
             nn.init.zeros_(head.weight)
             nn.init.zeros_(head.bias)
 
+    def _fused_parameters(self):
+        """The sixteen tensors in the order of grut_ppisp_controller_forward (the reference's flatten_controller_weights)."""
+        layers = (self.cnn_encoder[0], self.cnn_encoder[3], self.cnn_encoder[5], self.mlp_trunk[0], self.mlp_trunk[2], self.mlp_trunk[4],
+                  self.exposure_head, self.color_head)
+        return [p for layer in layers for p in (layer.weight, layer.bias)]
+
     def forward(self, hdr, prior):
-        """hdr [H, W, 3], prior [1] -> (exposure [], color [8])"""
+        """hdr [H, W, 3], prior [1] -> (exposure [], color [8]).  With install_fused_controller() on, an fp32 CUDA image that does not
+        require grad (nor does prior), with all sixteen parameters fp32, contiguous and on its device, runs csrc/ppisp_controller.hip;
+        every other input runs the torch code below."""
+        if _fused_controller:
+            params = self._fused_parameters()
+            if (torch.is_tensor(hdr) and hdr.is_cuda and hdr.dtype == torch.float32 and hdr.dim() == 3 and hdr.shape[2] == 3
+                    and min(hdr.shape[:2]) >= 3 and max(hdr.shape[:2]) <= 16384 and not hdr.requires_grad
+                    and torch.is_tensor(prior) and prior.numel() >= 1 and prior.device == hdr.device and not prior.requires_grad
+                    and all(p.is_cuda and p.device == hdr.device and p.dtype == torch.float32 and p.is_contiguous() for p in params)):
+                keep = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+                out = _ControllerApply.apply(hdr.contiguous(), prior.reshape(-1)[:1].to(torch.float32).contiguous(), keep, *params)
+                return out[0], out[1:]
+        stats["controller_torch_calls"] += 1
         features = self.cnn_encoder(hdr.permute(2, 0, 1).unsqueeze(0)).reshape(-1)
         trunk = self.mlp_trunk(torch.cat([features, prior.reshape(1).to(features.dtype)]))
         return self.exposure_head(trunk).reshape(()), self.color_head(trunk)

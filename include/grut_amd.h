@@ -680,6 +680,33 @@ int grut_ppisp_backward(void* stream, uint32_t num_pixels, const float* rgb, con
                         const float* exposure, const float* color, const float* vignetting, const float* crf, const float* grad_out,
                         float* grad_rgb, float* grad_exposure, float* grad_color, float* grad_vignetting, float* grad_crf, float* partials);
 
+/* ---- PPISP controller (3dgrut_amd/ppisp.py: _PPISPController) ------------------------------------------------------------------ */
+/* The per-camera network that predicts a frame's exposure and eight colour latents from the rendered image, all fp32:
+ *   hdr [h, w, 3] -> conv1x1 3->16 + bias -> max over non-overlapping 3x3 windows (dsH = h / 3, dsW = w / 3; remainder rows and columns
+ *   are dropped) -> ReLU -> conv1x1 16->32 + bias -> ReLU -> conv1x1 32->64 + bias -> adaptive average pool to 5x5 (cell g covers
+ *   [floor(g ds / 5), ceil((g + 1) ds / 5)) in each direction) -> feat[c * 25 + cell] ++ prior -> three Linear + ReLU 1601->128->128->128
+ *   -> exposure head 128->1 and colour head 128->8.
+ * weights: HOST array of 16 DEVICE pointers, each the contiguous [out][in] tensor as the module holds it, in the order
+ *   conv1 w, b; conv2 w, b; conv3 w, b; trunk0 w, b; trunk1 w, b; trunk2 w, b; exposure w, b; colour w, b.
+ *   They are read at every launch: nothing is flattened or cached between calls.  grads: the same array of 16 pointers to write.
+ * prior: DEVICE pointer to one float, read on the device (NULL: 0).  out[9]: exposure, then the colour latents.
+ * saved: NULL, or GRUT_PPISP_CONTROLLER_SAVED floats the forward writes for the backward: the 1600 pooled features, then the three
+ *   post-ReLU trunk activations.  A forward with saved == NULL gives the same bits in `out`.
+ * scratch: grut_ppisp_controller_{forward,backward}_scratch(h, w) floats that belong to the caller (host arithmetic; 0 for a shape that
+ *   is not taken); nothing has to be zeroed.
+ * The backward reads grad_out[9] from device memory and writes all 16 gradient tensors completely; the CNN part is recomputed from hdr.
+ * There is no gradient for hdr or prior.  A max-pool tie sends its gradient to the first maximum in row-major order within the window;
+ * a ReLU passes gradient where its input is > 0.
+ * No allocation, no synchronisation, no atomics: the order of every sum depends on (h, w) only, two calls on the same input are bitwise
+ * equal.  h < 3, w < 3, h or w above 16384 or a NULL among the required pointers is GRUT_ERR_BAD_INPUT before any HIP call. */
+#define GRUT_PPISP_CONTROLLER_SAVED 1984
+uint64_t grut_ppisp_controller_forward_scratch(int h, int w);
+uint64_t grut_ppisp_controller_backward_scratch(int h, int w);
+int grut_ppisp_controller_forward(void* stream, int h, int w, const float* hdr, const float* prior, const float* const* weights,
+                                  float* scratch, float* saved, float* out);
+int grut_ppisp_controller_backward(void* stream, int h, int w, const float* hdr, const float* prior, const float* const* weights,
+                                   const float* saved, const float* grad_out, float* scratch, float* const* grads);
+
 /* ---- NHT decoder network (threedgrut/model/feature_decoder.py: tinycudann's NetworkWithInputEncoding) -------------------------- */
 /* The network that turns a pixel's rendered features and ray direction into colour (model.feature_type: nht), forward only, as one
  * fused pass: encoding, every layer and the output activation, the activations never leaving registers.  The model, which is THIS
