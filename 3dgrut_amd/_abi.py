@@ -159,6 +159,14 @@ class GrutDecodeConfig(C.Structure):
     _fields_ = [("mlp", GrutMlpConfig), ("sh_scale", C.c_float), ("unpremultiply_alpha", C.c_int32), ("center_ray", C.c_int32)]
 
 
+class McmcTensor(C.Structure):   # GrutMcmcTensor
+    _fields_ = [("data", C.c_void_p), ("row_elems", C.c_uint32), ("role", C.c_uint32)]
+
+
+MCMC_MAX_TENSORS = 32                                                          # GRUT_MCMC_MAX_TENSORS
+MCMC_ROLE_COPY, MCMC_ROLE_NEW_DENSITY, MCMC_ROLE_NEW_SCALE, MCMC_ROLE_STATE = range(4)   # GRUT_MCMC_ROLE_*
+
+
 # every symbol include/grut_amd.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = [
     "gut_create", "gut_destroy", "gut_forward", "gut_backward", "gut_backward_unpacked", "gut_backward_factored", "gut_backward_factored_chunked", "grut_sph_grad_from_views", "gut_timings", "gut_stats",
@@ -169,6 +177,7 @@ EXPORTED_SYMBOLS = [
     "grt_debug_forward_hits", "grt_debug_fetch_instances", "grt_debug_fetch_custom_boxes", "grt_debug_fetch_lists", "grt_debug_backward_signature", "grt_build_mesh_bvh", "grt_trace_hybrid",
     "grut_selective_adam_update", "grut_pack_particles", "grut_unpack_particle_grads", "grut_activate_pack", "grut_activate_pack_backward",
     "grut_mcmc_relocation", "grut_mcmc_perturb",
+    "grut_mcmc_classify", "grut_mcmc_classify_scratch_bytes", "grut_mcmc_sample_plan", "grut_mcmc_relocate_rows", "grut_mcmc_append_rows",
     "grut_densify_accumulate", "grut_relayout_scan", "grut_relayout_scratch_bytes", "grut_relayout_rows", "grut_split_tail",
     "grut_ssim_forward", "grut_ssim_backward", "grut_ssim_partials",
     "grut_photo_loss_forward", "grut_photo_loss_backward", "grut_photo_loss_partials",
@@ -293,6 +302,17 @@ def _declare(lib):
     lib.grut_mcmc_relocation.restype = C.c_int
     lib.grut_mcmc_perturb.argtypes = [vp, C.c_uint32, fp, fp, fp, fp, fp, C.c_float, C.c_float, C.c_int]
     lib.grut_mcmc_perturb.restype = C.c_int
+    lib.grut_mcmc_classify.argtypes = [vp, C.c_uint32, fp, C.c_float, ip, ip, fp, up, vp, C.c_uint64]
+    lib.grut_mcmc_classify.restype = C.c_int
+    lib.grut_mcmc_classify_scratch_bytes.argtypes = [C.c_uint32]
+    lib.grut_mcmc_classify_scratch_bytes.restype = C.c_uint64
+    lib.grut_mcmc_sample_plan.argtypes = [vp, C.c_uint32, C.c_uint32, ip, ip, C.c_uint32, fp, fp, C.c_int, fp, C.c_int, C.c_float,
+                                          ip, ip, ip, fp, fp, fp, fp]
+    lib.grut_mcmc_sample_plan.restype = C.c_int
+    lib.grut_mcmc_relocate_rows.argtypes = [vp, C.POINTER(McmcTensor), C.c_uint32, C.c_uint32, ip, ip, ip, fp, fp]
+    lib.grut_mcmc_relocate_rows.restype = C.c_int
+    lib.grut_mcmc_append_rows.argtypes = [vp, C.POINTER(McmcTensor), C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32, ip, ip, ip, fp, fp]
+    lib.grut_mcmc_append_rows.restype = C.c_int
     lib.grut_densify_accumulate.argtypes = [vp, C.c_uint32, fp, fp, fp, C.c_int64, fp, ip]
     lib.grut_densify_accumulate.restype = C.c_int
     lib.grut_relayout_scan.argtypes = [vp, C.c_uint32, up, up, up, up, up, vp, C.c_uint64]

@@ -8,37 +8,24 @@
 //     over [N,3,3] / [N,3] temporaries.  HBM-bound: 56 B read (rotation 16, scale 12, density 4, noise 12, positions 12) and 12 B
 //     written per Gaussian.
 #include "common.hpp"
+#include "mcmc_device.inl"
 
 namespace grut {
 
 constexpr int kMcmcThreads = 256;
 
 // ---- relocation ------------------------------------------------------------------------------------------------------------------
-// new_opacity = 1 - (1 - o)^(1/n)
-// new_scale   = o / D * scale,  D = sum_{i=1..n} sum_{k=0..i-1} binoms[(i-1) n_max + k] (-1)^k / sqrt(k+1) new_opacity^(k+1)
-// D is an alternating sum that cancels by up to ~3 decades in fp32 at large n; the reference's result IS that fp32 sum in this order
-// (i outer, k inner, one running sum), so it is evaluated term by term and not through a closed form.
-// n is clamped to [1, n_max]: the reference's caller always clamps (mcmc.py:203-205) and the table holds n_max rows of n_max entries,
-// so the clamp keeps every binoms read inside [0, n_max^2) whatever the caller passes.
+// The formula itself is mcmc_relocation_values (mcmc_device.inl), shared with the event plan of mcmc_events.hip.
 __global__ __launch_bounds__(kMcmcThreads) void mcmc_relocation_kernel(uint32_t n, const float* __restrict__ opacities,
                                                                        const float* __restrict__ scales, const int32_t* __restrict__ ratios,
                                                                        const float* __restrict__ binoms, int n_max,
                                                                        float* __restrict__ new_opacities, float* __restrict__ new_scales) {
     const uint32_t idx = blockIdx.x * kMcmcThreads + threadIdx.x;
     if (idx >= n) return;
-    const int copies = min(max(ratios[idx], 1), n_max);
     const float o = opacities[idx];
-    const float new_o = 1.0f - powf(1.0f - o, 1.0f / (float)copies);
+    float new_o, coeff;
+    mcmc_relocation_values(o, ratios[idx], binoms, n_max, new_o, coeff);
     new_opacities[idx] = new_o;
-    float denom = 0.0f;
-    for (int i = 1; i <= copies; ++i) {
-        const float* row = binoms + (size_t)(i - 1) * (size_t)n_max;
-        for (int k = 0; k < i; ++k) {
-            const float term = ((k & 1) ? -1.0f : 1.0f) / sqrtf((float)(k + 1)) * powf(new_o, (float)(k + 1));
-            denom += row[k] * term;
-        }
-    }
-    const float coeff = o / denom;
     const size_t s = 3 * (size_t)idx;
     new_scales[s] = coeff * scales[s];
     new_scales[s + 1] = coeff * scales[s + 1];

@@ -567,6 +567,60 @@ int grut_mcmc_relocation(void* stream, uint32_t n, const float* opacities, const
 int grut_mcmc_perturb(void* stream, uint32_t n, float* positions, const float* rotation, const float* scale, const float* density,
                       const float* noise, float noise_lr, float lr, int activated);
 
+/* The strategy's two periodic events, relocate_gaussians and add_new_gaussians (mcmc.py:109-165, 189-224), as fused passes.  None of
+ * the four allocates, synchronises or uses float atomics; every buffer is a contiguous DEVICE buffer of the caller; zero rows launch
+ * nothing; row counts are below 2^31.  A NULL among the required pointers or a value out of range is GRUT_ERR_BAD_INPUT before any
+ * HIP call, and grut_last_error() names the argument. */
+/* Replaces the two torch.where of relocate_gaussians (mcmc.py:112-116) and the gather densities[alive_idxs].flatten() of
+ * sample_new_gaussians (mcmc.py:198).  density [n]: the ACTIVATED densities as the caller computed them.  dead_idx int64 [n]: ascending,
+ * the rows with density <= threshold; alive_idx int64 [n]: ascending, the rows with density > threshold (a NaN is in neither, as with
+ * torch.where); alive_prob [n]: density[alive_idx], copied as bits (what torch.multinomial is given); counts[2] = {n_dead, n_alive} in
+ * device memory.  Only the first n_dead / n_alive entries of the lists are written.  scratch: grut_mcmc_classify_scratch_bytes(n)
+ * bytes, 16-byte aligned. */
+int grut_mcmc_classify(void* stream, uint32_t n, const float* density, float threshold, int64_t* dead_idx, int64_t* alive_idx,
+                       float* alive_prob, uint32_t* counts, void* scratch, uint64_t scratch_bytes);
+uint64_t grut_mcmc_classify_scratch_bytes(uint32_t n);
+/* Replaces sample_new_gaussians after its torch.multinomial draw (mcmc.py:202-222): valid_indices[sampled], bincount and its gather
+ * and clamp, the gathers around compute_relocation_tensor, the relocation and the two inverse activations.
+ * sampled int64 [m]: the draws; index_map (optional) int64 [n_map]: source[j] = index_map[sampled[j]], otherwise sampled[j] (draws and
+ * mapped indices are clamped into their ranges, so nothing is accessed out of bounds).  density [n] ACTIVATED; scale [n,3] raw
+ * (scale_activated = 0: exp is applied here) or activated (1); binoms [n_max, n_max].
+ * Out: source int64 [m]; count int32 [n]: the histogram of source (cleared here); first int32 [n]: the smallest j with source[j] == i
+ * (INT32_MAX where count is 0); with ratio = clamp(count[source[j]] + 1, 1, n_max) and (new_o, new_s) the relocation of
+ * grut_mcmc_relocation (the same device function): new_density_act [m] = new_o and new_scale_act [m,3] = new_s (both optional),
+ * new_density_raw [m] = logf(x / (1 - x)) with x = min(max(new_o, threshold), 1 - FLT_EPSILON) and an IEEE division,
+ * new_scale_raw [m,3] = logf(new_s).  Draws of one source get bit-identical values. */
+int grut_mcmc_sample_plan(void* stream, uint32_t n, uint32_t m, const int64_t* sampled, const int64_t* index_map, uint32_t n_map,
+                          const float* density, const float* scale, int scale_activated, const float* binoms, int n_max, float threshold,
+                          int64_t* source, int32_t* count, int32_t* first, float* new_density_raw, float* new_scale_raw,
+                          float* new_density_act, float* new_scale_act);
+enum { GRUT_MCMC_MAX_TENSORS = 32 };
+enum { GRUT_MCMC_ROLE_COPY = 0,          /* a parameter whose rows are copied */
+       GRUT_MCMC_ROLE_NEW_DENSITY = 1,   /* the raw density [.,1]: sources and copies take new_density */
+       GRUT_MCMC_ROLE_NEW_SCALE = 2,     /* the raw scale [.,3]: sources and copies take new_scale */
+       GRUT_MCMC_ROLE_STATE = 3          /* an optimizer moment */ };
+typedef struct GrutMcmcTensor {
+    void* data;          /* [rows, row_elems] of 4-byte elements, moved as bits */
+    uint32_t row_elems;
+    uint32_t role;       /* GRUT_MCMC_ROLE_* */
+} GrutMcmcTensor;
+/* Replaces update_param_fn / update_optimizer_fn of relocate_gaussians (mcmc.py:121-131) as applied to every parameter and moment by
+ * strategy/base.py:77-107, IN PLACE and in ONE launch over all num_tensors <= 32 tensors (a host array, passed on by value).  With
+ * source / first / new_density [m] / new_scale [m,3] of grut_mcmc_sample_plan and dead_idx int64 [m] (distinct rows, none of them a source):
+ *   COPY     data[dead_idx[j]] = data[source[j]]
+ *   NEW_*    data[source[j]] = new[j], written by the j with first[source[j]] == j, and data[dead_idx[j]] = new[j]
+ *   STATE    data[source[j]] = 0 (dead rows keep their moments) */
+int grut_mcmc_relocate_rows(void* stream, const GrutMcmcTensor* tensors, uint32_t num_tensors, uint32_t m, const int64_t* source,
+                            const int64_t* dead_idx, const int32_t* first, const float* new_density, const float* new_scale);
+/* Replaces update_param_fn / update_optimizer_fn of add_new_gaussians (mcmc.py:148-158: the indexed write, torch.cat([param,
+ * param[sampled]]) and zeros + cat per moment) in ONE launch over all tensors: tensors[k].data [n, row_elems] -> outs[k] [n + m,
+ * row_elems] (must not overlap any input).
+ *   rows i < n    outs[i] = data[i]; NEW_*: new[first[i]] where count[i] > 0
+ *   rows n + j    COPY: data[source[j]]; NEW_*: new[j]; STATE: 0 */
+int grut_mcmc_append_rows(void* stream, const GrutMcmcTensor* tensors, void* const* outs, uint32_t num_tensors, uint32_t n, uint32_t m,
+                          const int64_t* source, const int32_t* count, const int32_t* first, const float* new_density,
+                          const float* new_scale);
+
 /* ---- default densification strategy (threedgrut/strategy/gs.py) ------------------------------------------------ */
 /* None of these allocates or synchronises; every tensor is a contiguous DEVICE tensor of the caller. */
 /* Replaces GSStrategy.update_gradient_buffer (gs.py:131-139) in one pass: for every row with a non-zero (or NaN) component of
