@@ -1,6 +1,7 @@
 // gut_api.hip — host orchestration of the 3DGUT path behind the C-ABI (include/grut_amd.h).
 // Plays the role of SplatRaster + GUTRenderer (threedgut_tracer/src/splatRaster.cpp:184-350,
 // src/gutRenderer.cu:241-520) without libtorch: all I/O buffers belong to the caller.
+#include <initializer_list>
 #include <vector>
 
 #include "gut_internal.hpp"
@@ -317,9 +318,10 @@ void gut_destroy(GutHandle* h) {
     delete h;
 }
 
-int gut_forward(GutHandle* h, void* stream_, const GutFrame* frame, const float* particle_density, const void* particle_sph_,
-                const float* ray_origin, const float* ray_direction, void* out_feat_density_, float* out_hit_distance,
-                float* out_hit_count, int32_t* out_visibility) {
+// gut_forward / gut_forward_split: the SH coefficients are particle_sph, or (split.specular) the model's two tensors
+static int forward_impl(GutHandle* h, void* stream_, const GutFrame* frame, const float* particle_density, const void* particle_sph_,
+                        const GutSplitSph& split, const float* ray_origin, const float* ray_direction, void* out_feat_density_,
+                        float* out_hit_distance, float* out_hit_count, int32_t* out_visibility) {
     // (fp32 buffers by default; IEEE half with particle_feature_half / feature_output_half: the kernels look at GutParams::sph_half / out_half)
     const float* particle_sph = reinterpret_cast<const float*>(particle_sph_);
     float* out_feat_density = reinterpret_cast<float*>(out_feat_density_);
@@ -348,7 +350,7 @@ int gut_forward(GutHandle* h, void* stream_, const GutFrame* frame, const float*
         h->have_forward = true;
         return GRUT_OK;
     }
-    GRUT_REQUIRE(particle_density && particle_sph && out_visibility, "gut_forward: null particle buffer");
+    GRUT_REQUIRE(particle_density && (particle_sph || split.specular) && out_visibility, "gut_forward: null particle buffer");
     GRUT_REQUIRE(!h->cfg.feature_output_half || (!frame->out_features && !frame->out_opacity), "gut_forward: feature_output_half excludes out_features / out_opacity");
     GRUT_REQUIRE(!h->cfg.feature_transform_type || (!frame->out_features && !frame->out_opacity), "gut_forward: neural harmonic features exclude out_features / out_opacity");
     if (h->cfg.enable_kernel_timings) GRUT_CHECK(h->fwd_timer.begin(s));
@@ -387,7 +389,7 @@ int gut_forward(GutHandle* h, void* stream_, const GutFrame* frame, const float*
     }
     // K1 projection
     GRUT_CHECK(h->stage_begin(GUT_STAGE_PROJECT, s, slot));
-    launch_project(s, P, particle_density, particle_sph, proj, out_visibility, d_counters + 1);
+    launch_project(s, P, particle_density, particle_sph, split, proj, out_visibility, d_counters + 1);
     GRUT_CHECK(h->stage_end(GUT_STAGE_PROJECT, s, slot));
     GRUT_CHECK(h->stage_begin(GUT_STAGE_DEPTH_SORT, s, slot));
     // K2 depth sort of the particles (N keys): rank order = (depth bits, particle index)
@@ -487,6 +489,40 @@ int gut_forward(GutHandle* h, void* stream_, const GutFrame* frame, const float*
     return GRUT_OK;
 }
 
+int gut_forward(GutHandle* h, void* stream, const GutFrame* frame, const float* particle_density, const void* particle_sph,
+                const float* ray_origin, const float* ray_direction, void* out_feat_density, float* out_hit_distance,
+                float* out_hit_count, int32_t* out_visibility) {
+    return forward_impl(h, stream, frame, particle_density, particle_sph, GutSplitSph{}, ray_origin, ray_direction, out_feat_density,
+                        out_hit_distance, out_hit_count, out_visibility);
+}
+
+// What the split entry points accept (include/grut_amd.h), checked before anything is launched or any state of the handle changes.
+static int split_preconditions(const GutHandle* h, const char* who, std::initializer_list<const void*> buffers) {
+    GRUT_REQUIRE(h, "%s: null handle", who);
+    const GutConfig& cfg = h->cfg;
+    const char* why = cfg.feature_transform_type ? "neural harmonic features have no albedo / specular tensors"
+                      : cfg.particle_feature_half ? "particle_feature_half (the model's tensors are fp32)"
+                      : cfg.particle_radiance_sph_degree != 3 ? "particle_radiance_sph_degree != 3 (the tensors are [N,3] and [N,45])"
+                      : cfg.k_buffer_size != 0 ? "k_buffer_size > 0 (the sorted mode runs on the [N,48] buffer)" : nullptr;
+    if (why) {
+        set_last_error("%s: unsupported configuration: %s", who, why);
+        return GRUT_ERR_UNSUPPORTED;
+    }
+    for (const void* p : buffers) {
+        GRUT_REQUIRE(p, "%s: null albedo / specular buffer", who);
+        GRUT_REQUIRE((reinterpret_cast<uintptr_t>(p) & 15u) == 0, "%s: the albedo / specular buffers must be 16-byte aligned", who);
+    }
+    return GRUT_OK;
+}
+
+int gut_forward_split(GutHandle* h, void* stream, const GutFrame* frame, const float* particle_density, const float* sph_albedo,
+                      const float* sph_specular, const float* ray_origin, const float* ray_direction, void* out_feat_density,
+                      float* out_hit_distance, float* out_hit_count, int32_t* out_visibility) {
+    GRUT_CHECK(split_preconditions(h, "gut_forward_split", {sph_albedo, sph_specular}));
+    return forward_impl(h, stream, frame, particle_density, nullptr, GutSplitSph{sph_albedo, sph_specular}, ray_origin, ray_direction,
+                        out_feat_density, out_hit_distance, out_hit_count, out_visibility);
+}
+
 // The gradient slots of a backward over I tile entries: the partials and both levels of marks (GutGradSlots).  Marks are not cleared per
 // backward - the finalisation leaves them zero - only when their buffer is new (first use, growth, after gut_trim) or the handle is dirty.
 static int prepare_grad_slots(GutHandle* h, hipStream_t s, size_t I, GutGradSlots& slots) {
@@ -508,7 +544,8 @@ static int backward_impl(GutHandle* h, void* stream_, const GutFrame* frame, con
                          const float* ray_origin, const float* ray_direction, const void* feat_density_, const float* grad_feat_density,
                          const float* hit_distance, const float* grad_hit_distance, float* grad_particle_density, float* grad_particle_sph,
                          float* grad_radiance, const GutGradIO* io = nullptr, uint32_t num_chunks = 1, GrutChunkFn on_chunk = nullptr,
-                         void* chunk_user = nullptr) {
+                         void* chunk_user = nullptr, const GutSplitSph& split = {}, const GutSplitSphGrad& g_split = {}) {
+    // (split / g_split, gut_backward*_split: the model's two SH tensors and their gradients in place of particle_sph / grad_particle_sph)
     const float* particle_sph = reinterpret_cast<const float*>(particle_sph_);       // (fp32, or half with particle_feature_half)
     const float* feat_density = reinterpret_cast<const float*>(feat_density_);       // (fp32, or half with feature_output_half)
     GRUT_REQUIRE(h && frame, "gut_backward: null handle/frame");
@@ -594,8 +631,8 @@ static int backward_impl(GutHandle* h, void* stream_, const GutFrame* frame, con
             return GRUT_ERR_UNSUPPORTED;
         }
     }
-    GRUT_REQUIRE(particle_density && particle_sph && feat_density && (io || grad_feat_density) && hit_distance && (io || grad_particle_density) &&
-                     (grad_particle_sph || grad_radiance), "gut_backward: null buffer");  // grad_hit_distance may be NULL (no depth gradient)
+    GRUT_REQUIRE(particle_density && (particle_sph || split.specular) && feat_density && (io || grad_feat_density) && hit_distance &&
+                     (io || grad_particle_density) && (grad_particle_sph || grad_radiance || g_split.specular), "gut_backward: null buffer");  // grad_hit_distance may be NULL (no depth gradient)
     if (h->cfg.enable_kernel_timings) GRUT_CHECK(h->bwd_timer.begin(s));
     const GutProjected proj = projected_view(h);
     const int slot = h->prof_fwd_slot;
@@ -621,7 +658,7 @@ static int backward_impl(GutHandle* h, void* stream_, const GutFrame* frame, con
             GRUT_CHECK(h->stage_end(GUT_STAGE_RENDER_BWD, s, slot));
         }
         GRUT_CHECK(h->stage_begin(GUT_STAGE_PROJECT_BWD, s, slot));
-        launch_project_bwd(s, P, proj, particle_density, particle_sph, h->g_rgb.as<float>(), g_out, grad_particle_sph, grad_radiance);
+        launch_project_bwd(s, P, proj, particle_density, particle_sph, split, h->g_rgb.as<float>(), g_out, grad_particle_sph, g_split, grad_radiance);
         GRUT_CHECK(h->stage_end(GUT_STAGE_PROJECT_BWD, s, slot));
         GRUT_HIP(hipGetLastError());
         if (h->cfg.enable_kernel_timings) GRUT_CHECK(h->bwd_timer.end(s));
@@ -638,8 +675,8 @@ static int backward_impl(GutHandle* h, void* stream_, const GutFrame* frame, con
     GRUT_CHECK(h->stage_begin(GUT_STAGE_PROJECT_BWD, s, slot));
     GRUT_CHECK(h->g_rgb.ensure((size_t)P.N * 12, 1.25f));  // per-particle radiance gradient between gather and SH backward
     if (num_chunks <= 1 || !on_chunk) {
-        launch_grad_finalize(s, P, proj, particle_density, particle_sph, slots, has_gdist, I > 0, h->g_rgb.as<float>(), g_out,
-                             grad_particle_sph, grad_radiance);
+        launch_grad_finalize(s, P, proj, particle_density, particle_sph, split, slots, has_gdist, I > 0, h->g_rgb.as<float>(), g_out,
+                             grad_particle_sph, g_split, grad_radiance);
     } else {
         // pipelined exchange: the finalisation runs chunk by chunk over the particle range (chunks start at multiples of 128: the
         // projection backward's workgroup) and the caller is told after each chunk's launches - it issues that chunk's collectives, which
@@ -648,8 +685,8 @@ static int backward_impl(GutHandle* h, void* stream_, const GutFrame* frame, con
         uint32_t c = 0;
         for (uint32_t first = 0; first < P.N; first += per, ++c) {
             const uint32_t end = first + per < P.N ? first + per : P.N;
-            launch_grad_finalize(s, P, proj, particle_density, particle_sph, slots, has_gdist, I > 0, h->g_rgb.as<float>(), g_out,
-                                 grad_particle_sph, grad_radiance, first, end);
+            launch_grad_finalize(s, P, proj, particle_density, particle_sph, split, slots, has_gdist, I > 0, h->g_rgb.as<float>(), g_out,
+                                 grad_particle_sph, g_split, grad_radiance, first, end);
             on_chunk(chunk_user, c, first, end - first);
         }
     }
@@ -673,6 +710,27 @@ int gut_backward_unpacked(GutHandle* h, void* stream, const GutFrame* frame, con
     GRUT_REQUIRE(io, "gut_backward_unpacked: null GutGradIO");
     return backward_impl(h, stream, frame, particle_density, particle_sph, ray_origin, ray_direction, feat_density, nullptr, hit_distance,
                          grad_hit_distance, nullptr, grad_particle_sph, nullptr, io);
+}
+
+int gut_backward_split(GutHandle* h, void* stream, const GutFrame* frame, const float* particle_density, const float* sph_albedo,
+                       const float* sph_specular, const float* ray_origin, const float* ray_direction, const void* feat_density,
+                       const float* grad_feat_density, const float* hit_distance, const float* grad_hit_distance, float* grad_particle_density,
+                       float* grad_sph_albedo, float* grad_sph_specular) {
+    GRUT_CHECK(split_preconditions(h, "gut_backward_split", {sph_albedo, sph_specular, grad_sph_albedo, grad_sph_specular}));
+    return backward_impl(h, stream, frame, particle_density, nullptr, ray_origin, ray_direction, feat_density, grad_feat_density, hit_distance,
+                         grad_hit_distance, grad_particle_density, nullptr, nullptr, nullptr, 1, nullptr, nullptr,
+                         GutSplitSph{sph_albedo, sph_specular}, GutSplitSphGrad{grad_sph_albedo, grad_sph_specular});
+}
+
+int gut_backward_unpacked_split(GutHandle* h, void* stream, const GutFrame* frame, const float* particle_density, const float* sph_albedo,
+                                const float* sph_specular, const float* ray_origin, const float* ray_direction, const void* feat_density,
+                                const float* hit_distance, const float* grad_hit_distance, const GutGradIO* io, float* grad_sph_albedo,
+                                float* grad_sph_specular) {
+    GRUT_CHECK(split_preconditions(h, "gut_backward_unpacked_split", {sph_albedo, sph_specular, grad_sph_albedo, grad_sph_specular}));
+    GRUT_REQUIRE(io, "gut_backward_unpacked_split: null GutGradIO");
+    return backward_impl(h, stream, frame, particle_density, nullptr, ray_origin, ray_direction, feat_density, nullptr, hit_distance,
+                         grad_hit_distance, nullptr, nullptr, nullptr, io, 1, nullptr, nullptr, GutSplitSph{sph_albedo, sph_specular},
+                         GutSplitSphGrad{grad_sph_albedo, grad_sph_specular});
 }
 
 int gut_backward_factored(GutHandle* h, void* stream, const GutFrame* frame, const float* particle_density, const void* particle_sph,

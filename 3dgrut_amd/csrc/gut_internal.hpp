@@ -90,6 +90,16 @@ struct GutGradIn {
     const float* rgb;
     const float* opa;
 };
+// The SH coefficients as the model's two tensors (gut_forward_split / gut_backward*_split) and their gradients: virtual float e of
+// particle i's 48-float row is albedo[3 i + e] for e < 3 and specular[45 i + e - 3] otherwise.  specular == nullptr: one [N,48] buffer.
+struct GutSplitSph {
+    const float* albedo = nullptr;     // [N,3]
+    const float* specular = nullptr;   // [N,45]
+};
+struct GutSplitSphGrad {
+    float* albedo = nullptr;
+    float* specular = nullptr;
+};
 #ifdef __HIPCC__
 __device__ __forceinline__ float4 load_grad_in(const GutGradIn& g, size_t pix) {
     if (g.fd) return reinterpret_cast<const float4*>(g.fd)[pix];
@@ -123,7 +133,7 @@ struct GutCheckpoints {
 // the visible-particle counter is replicated: 15.6 k waves adding to ONE word serialise in the L2 (measured: 0.13 of the projection's
 // 0.21 ms); a wave adds to replica (workgroup mod 64), each on its own 128-byte line, the tail preparation sums and re-arms them
 constexpr uint32_t kGutCounterReplicas = 64, kGutCounterStride = 32, kGutCounterWords = kGutCounterReplicas * kGutCounterStride + 32;
-void launch_project(hipStream_t s, const GutParams& P, const float* density12, const float* sph, const GutProjected& out,
+void launch_project(hipStream_t s, const GutParams& P, const float* density12, const float* sph, const GutSplitSph& split, const GutProjected& out,
                     int32_t* visibility, uint32_t* num_visible);
 void launch_expand(hipStream_t s, const GutParams& P, const GutProjected& proj, const uint32_t* rank_to_particle,
                    const uint32_t* offsets, uint32_t capacity, uint32_t* tile_keys, uint32_t* tile_vals, uint32_t* pos_particle);
@@ -162,10 +172,12 @@ void launch_render_k_bwd(hipStream_t s, const GutParams& P, const uint32_t* rang
                          const float* density12, const float* rgb, const float* ray_o, const float* ray_d, const float* fd, const float* g_fd,
                          const float* dist, const float* g_dist, float* g_density12, float* g_rgb);
 void launch_project_bwd(hipStream_t s, const GutParams& P, const GutProjected& proj, const float* density12, const float* sph,
-                        const float* g_rgb, const GutGradOut& g_out, float* g_sph, float* g_radiance, uint32_t first = 0u, uint32_t end = 0xFFFFFFFFu);
+                        const GutSplitSph& split, const float* g_rgb, const GutGradOut& g_out, float* g_sph, const GutSplitSphGrad& g_split,
+                        float* g_radiance, uint32_t first = 0u, uint32_t end = 0xFFFFFFFFu);
 void launch_grad_finalize(hipStream_t s, const GutParams& P, const GutProjected& proj, const float* density12, const float* sph,
-                          const GutGradSlots& slots, bool has_gdist, bool have_partials, float* g_rgb, const GutGradOut& g_out, float* g_sph,
-                          float* g_radiance, uint32_t first = 0u, uint32_t end = 0xFFFFFFFFu);
+                          const GutSplitSph& split, const GutGradSlots& slots, bool has_gdist, bool have_partials, float* g_rgb,
+                          const GutGradOut& g_out, float* g_sph, const GutSplitSphGrad& g_split, float* g_radiance, uint32_t first = 0u,
+                          uint32_t end = 0xFFFFFFFFu);
 void launch_sph_grad_from_views(hipStream_t s, uint32_t N, uint32_t n_views, const float* factors, const float* positions, uint32_t pos_stride,
                                 int n_active, int ncoef, float scale, float* g_sph);
 

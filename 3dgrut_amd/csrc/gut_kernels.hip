@@ -295,19 +295,27 @@ __device__ __forceinline__ int group_source(int lane, bool member, const GroupPi
     return shift | (act ? (__ffsll((long long)mine) - 1) : 0);
 }
 
+// Four floats at a 4-byte boundary, moved as ONE global_load_dwordx4 / global_store_dwordx4 (global memory takes multi-dword accesses
+// at dword alignment; LDS would not).  For the 180-byte rows of the model's specular tensor (GutSplitSph).
+struct __attribute__((packed, aligned(4))) Float4A4 {
+    float x, y, z, w;
+};
+
 // ---------------------------------------------------------------------------------------------
 // K1: projection onto tiles — GUTProjector::eval (gutProjector.cuh:217-322)
 // ---------------------------------------------------------------------------------------------
 // 6 waves/SIMD measured best (0.227 ms; 4: 0.239, 5: 0.232, 8: 0.261 with spills).  One instantiation per (camera model, global /
 // rolling shutter): with the three models and the shutter iterations in one body the kernel was 17 k instructions (140 KB of code
 // against a 64 KB instruction cache shared by two CUs).
-template <int MODEL, int ROLLING>
+template <int MODEL, int ROLLING, bool SPLIT = false>
 #ifndef GRUT_PROJECT_WAVES_MAX
 #define GRUT_PROJECT_WAVES_MAX 6   // (8 fits the specialised kernels, 60 VGPRs, and changes nothing: 0.122 vs 0.120 ms)
 #endif
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, GRUT_PROJECT_WAVES_MAX))) void gut_project_kernel(GutParams P, const float4* __restrict__ density12,
                                                           const float* __restrict__ sph, GutProjected out,
-                                                          int32_t* __restrict__ visibility, uint32_t* __restrict__ num_visible) {
+                                                          int32_t* __restrict__ visibility, uint32_t* __restrict__ num_visible,
+                                                          const float* __restrict__ sph_specular) {
+    // SPLIT (gut_forward_split): sph is the model's albedo tensor [N,3] and sph_specular its [N,45] rest (GutSplitSph)
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const FramePoses& FP = frame_poses(P);
@@ -463,7 +471,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, GRUT_PRO
             const int nact = (P.n_active + 1) * (P.n_active + 1);
             const float* coef = sph + (size_t)i * 3 * P.ncoef;
             float r = 0.f, g = 0.f, bl = 0.f;
-            if (P.nht) {        // per-ray features: no per-particle radiance (gutProjector.cuh:306)
+            if (SPLIT) {
+                // split rows (fp32, 16 coefficients): coefficient 0 from the albedo row, coefficients 1 .. nact-1 = the first 3 (nact - 1)
+                // floats of the 180-byte specular row, which begins on a 4-byte boundary only - dword-aligned 16-byte loads, a last
+                // odd float on its own, nothing read that the chain below does not use; same fmaf chain, same coefficient order
+                const float* al = sph + 3 * (size_t)i;
+                const float* sp = sph_specular + 45 * (size_t)i;
+                float acc[3] = {fmaf(basis[0], al[0], 0.f), fmaf(basis[0], al[1], 0.f), fmaf(basis[0], al[2], 0.f)};
+                // 3 (nact - 1) = 0, 9, 24 or 45 specular floats: 0, 2, 6 or 11 whole words, and float 8 / float 44 (the blue of the last
+                // active coefficient, last in its chain) on its own
+                const int nq = (3 * (min(nact, 16) - 1)) >> 2;
+#pragma unroll
+                for (int q = 0; q < 11; ++q) {
+                    if (q < nq) {
+                        const Float4A4 v = reinterpret_cast<const Float4A4*>(sp)[q];
+                        const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc[(4 * q + j) % 3] = fmaf(basis[1 + (4 * q + j) / 3], e[j], acc[(4 * q + j) % 3]);
+                    }
+                }
+                if (nact == 4) acc[2] = fmaf(basis[3], sp[8], acc[2]);
+                else if (nact >= 16) acc[2] = fmaf(basis[15], sp[44], acc[2]);
+                r = acc[0]; g = acc[1]; bl = acc[2];
+            } else if (P.nht) {        // per-ray features: no per-particle radiance (gutProjector.cuh:306)
                 r = g = bl = -0.5f;
             } else if (P.sph_half) {   // PARTICLE_FEATURE_HALF: the coefficients are stored as IEEE half, the arithmetic stays fp32
                 const __half* hc = reinterpret_cast<const __half*>(sph) + (size_t)i * 3 * P.ncoef;
@@ -816,11 +846,38 @@ __device__ __forceinline__ float xor_sum_quads(float v) {  // sum over the 16 qu
 // kernel so that their round trip lies under the mask -> row chain.  Rows of particles without tiles are not read (a third of them) and
 // their gradient rows are written as zeros.  Saves a launch, the g_rgb round trip, the second read of the particle rows and the
 // read-modify-write of the position gradient.
-template <int STRIDE, bool NHT = false, bool FUSE_SH = false>
+// SPLIT (with FUSE_SH; gut_backward*_split): the rows are the model's two tensors (GutSplitSph) - sph / g_sph are the albedo tensor [N,3]
+// and its gradient, sph_specular / g_sph_specular the [N,45] one and its gradient.  Lane c still owns virtual floats [12 c, 12 c + 12):
+// lanes 1..3 specular[12 c - 3, 12 c + 9) of the row, lane 0 the albedo row and specular[0, 9).  A specular row is 180 bytes and begins
+// on a 4-byte boundary only, so the 16-byte words become dword-aligned global_load / global_store_dwordx4 (Float4A4).  Loads: three words
+// per lane as before - lane 0's third is specular[5, 9), which overlaps its second and stays inside the row - plus lane 0's dwordx3 of
+// albedo: four requests where the [N,48] form has three, 16 bytes per particle read twice.  Stores: two words that all four lanes
+// share, a third for lanes 1..3, and a dword + dwordx3 for lane 0: five requests, exactly the row's bytes.  No LDS, no barrier, the
+// twin's 80 VGPRs and 6 waves per SIMD (STRIDE 16), and rows of particles without tiles are still not read.  (The alternative - the
+// wave's 16 rows staged through LDS as one aligned block - reads those rows too and adds LDS, a barrier and per-element row / column
+// arithmetic to every wave; with lane 0's words loaded by a separate dword + two words the kernel took 82 VGPRs, 5 waves.)
+__device__ __forceinline__ void store_split_sh_part(float* __restrict__ g_albedo, float* __restrict__ g_specular, size_t i, int c, const float (&o)[12]) {
+    const bool first = c == 0;
+    float* sp = g_specular + 45 * i + (first ? 0 : 12 * c - 3);
+    Float4A4* w = reinterpret_cast<Float4A4*>(sp);
+    w[0] = first ? Float4A4{o[3], o[4], o[5], o[6]} : Float4A4{o[0], o[1], o[2], o[3]};
+    w[1] = first ? Float4A4{o[7], o[8], o[9], o[10]} : Float4A4{o[4], o[5], o[6], o[7]};
+    if (first) {
+        sp[8] = o[11];
+        float* al = g_albedo + 3 * i;
+        al[0] = o[0]; al[1] = o[1]; al[2] = o[2];
+    } else {
+        w[2] = Float4A4{o[8], o[9], o[10], o[11]};
+    }
+}
+template <int STRIDE, bool NHT = false, bool FUSE_SH = false, bool SPLIT = false>
 __global__ __launch_bounds__(256) void gut_grad_gather_kernel(GutParams P, GutProjected proj, const float4* __restrict__ density12,
                                                               GutGradSlots slots, int have_partials, GutGradOut g_out,
                                                               float* __restrict__ g_rgb, uint32_t first, uint32_t end,
-                                                              const float* __restrict__ sph = nullptr, float* __restrict__ g_sph = nullptr) {
+                                                              const float* __restrict__ sph = nullptr, float* __restrict__ g_sph = nullptr,
+                                                              const float* __restrict__ sph_specular = nullptr,
+                                                              float* __restrict__ g_sph_specular = nullptr) {
+    static_assert(!SPLIT || FUSE_SH, "split rows exist in the fused finalisation only");
     // particles [first, end): the whole scene, or one chunk of the pipelined gradient exchange (gut_backward_factored_chunked)
     const int lane = threadIdx.x & 63, c = threadIdx.x & 3;
     const uint32_t i = first + blockIdx.x * 64u + (threadIdx.x >> 2);
@@ -839,8 +896,24 @@ __global__ __launch_bounds__(256) void gut_grad_gather_kernel(GutParams P, GutPr
     float4 sh0 = make_float4(0.f, 0.f, 0.f, 0.f), sh1 = sh0, sh2 = sh0, pa = sh0;
     f3 rad = mk3(0.f, 0.f, 0.f);
     if (FUSE_SH && has) {
-        const float4* row = reinterpret_cast<const float4*>(sph + 48 * (size_t)i) + 3 * c;
-        sh0 = row[0]; sh1 = row[1]; sh2 = row[2];
+        if (SPLIT) {
+            const float* sp = sph_specular + 45 * (size_t)i + (c == 0 ? 0 : 12 * c - 3);
+            // (lane 0's third word is specular[5, 9): it overlaps the second and stays inside the row; only its last float is used)
+            const Float4A4 v0 = reinterpret_cast<const Float4A4*>(sp)[0], v1 = reinterpret_cast<const Float4A4*>(sp)[1];
+            const Float4A4 v2 = *reinterpret_cast<const Float4A4*>(sp + (c == 0 ? 5 : 8));
+            sh0 = make_float4(v0.x, v0.y, v0.z, v0.w);
+            sh1 = make_float4(v1.x, v1.y, v1.z, v1.w);
+            sh2 = make_float4(v2.x, v2.y, v2.z, v2.w);
+            if (c == 0) {
+                const float* al = sph + 3 * (size_t)i;
+                sh0 = make_float4(al[0], al[1], al[2], v0.x);
+                sh1 = make_float4(v0.y, v0.z, v0.w, v1.x);
+                sh2 = make_float4(v1.y, v1.z, v1.w, v2.w);
+            }
+        } else {
+            const float4* row = reinterpret_cast<const float4*>(sph + 48 * (size_t)i) + 3 * c;
+            sh0 = row[0]; sh1 = row[1]; sh2 = row[2];
+        }
         pa = density12[3 * (size_t)i];
         rad = mk3(proj.rgb[3 * (size_t)i], proj.rgb[3 * (size_t)i + 1], proj.rgb[3 * (size_t)i + 2]);
     }
@@ -918,8 +991,13 @@ __global__ __launch_bounds__(256) void gut_grad_gather_kernel(GutParams P, GutPr
     if (i >= end) return;
     float4* gd = reinterpret_cast<float4*>(g_out.packed + 12 * (size_t)i);
     if (FUSE_SH && !has) {
-        float4* out = reinterpret_cast<float4*>(g_sph + 48 * (size_t)i) + 3 * c;
-        out[0] = out[1] = out[2] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (SPLIT) {
+            const float zero[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            store_split_sh_part(g_sph, g_sph_specular, (size_t)i, c, zero);
+        } else {
+            float4* out = reinterpret_cast<float4*>(g_sph + 48 * (size_t)i) + 3 * c;
+            out[0] = out[1] = out[2] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
     }
     if (!has) {
         if (g_out.packed) {
@@ -990,10 +1068,14 @@ __global__ __launch_bounds__(256) void gut_grad_gather_kernel(GutParams P, GutPr
         gdir = sh_sum(gdir, mk3(quad_bcast_xor<2>(gdir.x), quad_bcast_xor<2>(gdir.y), quad_bcast_xor<2>(gdir.z)));   // their sum
         const f3 gsh = sh_position_gradient(dir, ilen, gdir);
         gpos_out = mk3(add_rn(gpos.x, gsh.x), add_rn(gpos.y, gsh.y), add_rn(gpos.z, gsh.z));
-        float4* out = reinterpret_cast<float4*>(g_sph + 48 * (size_t)i) + 3 * c;
-        out[0] = make_float4(o[0], o[1], o[2], o[3]);
-        out[1] = make_float4(o[4], o[5], o[6], o[7]);
-        out[2] = make_float4(o[8], o[9], o[10], o[11]);
+        if (SPLIT) {
+            store_split_sh_part(g_sph, g_sph_specular, (size_t)i, c, o);
+        } else {
+            float4* out = reinterpret_cast<float4*>(g_sph + 48 * (size_t)i) + 3 * c;
+            out[0] = make_float4(o[0], o[1], o[2], o[3]);
+            out[1] = make_float4(o[4], o[5], o[6], o[7]);
+            out[2] = make_float4(o[8], o[9], o[10], o[11]);
+        }
     }
     if (FUSE_SH) {
         if (c == 0) {
@@ -1035,12 +1117,20 @@ constexpr int kShStride = 49;
 // expanded here (192 B per particle); the view-specific factor g — the radiance gradient behind the clamp — is written to
 // g_radiance [N+1,3] instead, with the sensor position of the view in row N, and grut_sph_grad_from_views rebuilds the sum
 // over views after the factors have been gathered.  The view-direction part of the position gradient stays here.
-template <bool FACTORED>
+// SPLIT (gut_backward*_split with GRUT_GUT_UNFUSED_FINALIZE=1; fp32, 16 coefficients): sph / g_sph are the model's albedo tensor [N,3] and
+// its gradient, sph_specular / g_sph_specular the [N,45] one and its gradient (GutSplitSph).  Only the address maps of the two stages
+// differ: a wave's 64 specular rows are one contiguous block of 64 x 45 floats that begins on a 16-byte boundary (64 x 180 bytes per
+// wave), moved as float4 whose elements land at column 3 + e % 45 of row e / 45 - a last partial word of the scene's last wave goes
+// float by float - and its 64 x 3 albedo floats move one per lane and step.
+template <bool FACTORED, bool SPLIT = false>
 __global__ __launch_bounds__(128) void gut_project_bwd_kernel(GutParams P, const uint32_t* __restrict__ tiles_count,
                                                               const float4* __restrict__ density12, const float* __restrict__ sph,
                                                               const float* __restrict__ rgb, const float* __restrict__ g_rgb,
                                                               GutGradOut g_out, float* __restrict__ g_sph,
-                                                              float* __restrict__ g_radiance, uint32_t first, uint32_t end) {
+                                                              float* __restrict__ g_radiance, uint32_t first, uint32_t end,
+                                                              const float* __restrict__ sph_specular = nullptr,
+                                                              float* __restrict__ g_sph_specular = nullptr) {
+    static_assert(!SPLIT || !FACTORED, "the factored gradient has no split form");
     __shared__ float s_rows[2][64 * kShStride];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t wave_base = first + blockIdx.x * 128u + (uint32_t)wave * 64u;   // particles [first, end), first a multiple of 128
@@ -1054,7 +1144,34 @@ __global__ __launch_bounds__(128) void gut_project_bwd_kernel(GutParams P, const
     const int nrows = (int)min(64u, end > wave_base ? end - wave_base : 0u);
     // stage in.  48-float rows: the wave's rows are one contiguous, 16-byte aligned block, copied as independent float4
     // requests (12 per lane in flight); rows of particles without tiles ride along.  Other row lengths: one row per step.
-    if (P.sph_half) {
+    if (SPLIT) {
+        if (has_mask) {
+            const float* sp = sph_specular + (size_t)wave_base * 45;
+            const int total = nrows * 45;
+#pragma unroll
+            for (int it = 0; it < 12; ++it) {
+                const int f = 4 * (lane + 64 * it);
+                float e[4] = {0.f, 0.f, 0.f, 0.f};
+                if (f + 4 <= total) {
+                    const float4 v = reinterpret_cast<const float4*>(sp)[lane + 64 * it];
+                    e[0] = v.x; e[1] = v.y; e[2] = v.z; e[3] = v.w;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (f + j < total) e[j] = sp[f + j];
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (f + j < total) rows[((f + j) / 45) * kShStride + 3 + (f + j) % 45] = e[j];
+            }
+            const float* al = sph + (size_t)wave_base * 3;
+#pragma unroll
+            for (int it = 0; it < 3; ++it) {
+                const int f = lane + 64 * it;
+                if (f < 3 * nrows) rows[(f / 3) * kShStride + f % 3] = al[f];
+            }
+        }
+    } else if (P.sph_half) {
         const __half* hs = reinterpret_cast<const __half*>(sph);
         for (unsigned long long m = has_mask; m;) {
             const int row = __ffsll((long long)m) - 1;
@@ -1136,7 +1253,30 @@ __global__ __launch_bounds__(128) void gut_project_bwd_kernel(GutParams P, const
     }
     __syncthreads();
     // stage out: every row of the wave, zeros included (the caller does not pre-fill grad_sph)
-    if (rowlen == 48) {
+    if (SPLIT) {
+        float* sp = g_sph_specular + (size_t)wave_base * 45;
+        const int total = nrows * 45;
+#pragma unroll
+        for (int it = 0; it < 12; ++it) {
+            const int f = 4 * (lane + 64 * it);
+            float e[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) e[j] = f + j < total ? rows[((f + j) / 45) * kShStride + 3 + (f + j) % 45] : 0.f;
+            if (f + 4 <= total) {
+                reinterpret_cast<float4*>(sp)[lane + 64 * it] = make_float4(e[0], e[1], e[2], e[3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (f + j < total) sp[f + j] = e[j];
+            }
+        }
+        float* al = g_sph + (size_t)wave_base * 3;
+#pragma unroll
+        for (int it = 0; it < 3; ++it) {
+            const int f = lane + 64 * it;
+            if (f < 3 * nrows) al[f] = rows[(f / 3) * kShStride + f % 3];
+        }
+    } else if (rowlen == 48) {
         float4* dst = reinterpret_cast<float4*>(g_sph + (size_t)wave_base * 48);
         const int total4 = nrows * 12;
 #pragma unroll
@@ -1241,11 +1381,18 @@ void launch_prepare_tail(hipStream_t s, const uint32_t* last_offset, uint32_t* n
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-void launch_project(hipStream_t s, const GutParams& P, const float* density12, const float* sph, const GutProjected& out,
+void launch_project(hipStream_t s, const GutParams& P, const float* density12, const float* sph, const GutSplitSph& split, const GutProjected& out,
                     int32_t* visibility, uint32_t* num_visible) {
-#define GRUT_PROJECT_LAUNCH(M_, R_)                                                                                                          \
-    hipLaunchKernelGGL((gut_project_kernel<M_, R_>), dim3(div_up(P.N, 256)), dim3(256), 0, s, P, reinterpret_cast<const float4*>(density12), \
-                       sph, out, visibility, num_visible)
+    // (the split form is an instantiation of its own: the kernels of the [N,48] buffer keep their code, registers and scratch)
+#define GRUT_PROJECT_LAUNCH(M_, R_)                                                                                                                 \
+    do {                                                                                                                                            \
+        if (split.specular)                                                                                                                         \
+            hipLaunchKernelGGL((gut_project_kernel<M_, R_, true>), dim3(div_up(P.N, 256)), dim3(256), 0, s, P,                                      \
+                               reinterpret_cast<const float4*>(density12), split.albedo, out, visibility, num_visible, split.specular);           \
+        else                                                                                                                                        \
+            hipLaunchKernelGGL((gut_project_kernel<M_, R_, false>), dim3(div_up(P.N, 256)), dim3(256), 0, s, P,                                     \
+                               reinterpret_cast<const float4*>(density12), sph, out, visibility, num_visible, static_cast<const float*>(nullptr)); \
+    } while (0)
     const bool rolling = P.cam.shutter != GRUT_SHUTTER_GLOBAL;
     switch (P.cam.model) {
     case GRUT_CAMERA_OPENCV_PINHOLE: if (rolling) GRUT_PROJECT_LAUNCH(GRUT_CAMERA_OPENCV_PINHOLE, 1); else GRUT_PROJECT_LAUNCH(GRUT_CAMERA_OPENCV_PINHOLE, 0); break;
@@ -1271,10 +1418,15 @@ void launch_tile_ranges(hipStream_t s, uint32_t n, const uint32_t* n_dev, uint32
 
 // exactly one of g_sph (expanded SH gradient) and g_radiance (view factor, see gut_project_bwd_kernel<true>) is non-null
 void launch_project_bwd(hipStream_t s, const GutParams& P, const GutProjected& proj, const float* density12, const float* sph,
-                        const float* g_rgb, const GutGradOut& g_out, float* g_sph, float* g_radiance, uint32_t first, uint32_t end) {
+                        const GutSplitSph& split, const float* g_rgb, const GutGradOut& g_out, float* g_sph, const GutSplitSphGrad& g_split,
+                        float* g_radiance, uint32_t first, uint32_t end) {
     if (end > P.N) end = P.N;
     if (end <= first) return;
-    if (g_radiance)
+    if (split.specular)   // (the API admits the pair with fp32 rows of 16 coefficients and the expanded gradient only)
+        hipLaunchKernelGGL((gut_project_bwd_kernel<false, true>), dim3(div_up(end - first, 128)), dim3(128), 0, s, P, proj.tiles_count,
+                           reinterpret_cast<const float4*>(density12), split.albedo, proj.rgb, g_rgb, g_out, g_split.albedo, g_radiance, first, end,
+                           split.specular, g_split.specular);
+    else if (g_radiance)
         hipLaunchKernelGGL(gut_project_bwd_kernel<true>, dim3(div_up(end - first, 128)), dim3(128), 0, s, P, proj.tiles_count,
                            reinterpret_cast<const float4*>(density12), sph, proj.rgb, g_rgb, g_out, g_sph, g_radiance, first, end);
     else
@@ -1293,13 +1445,22 @@ void launch_grad_finalize_nht(hipStream_t s, const GutParams& P, const GutProjec
                        slots, have_partials ? 1 : 0, g_out, static_cast<float*>(nullptr), 0u, P.N);
 }
 void launch_grad_finalize(hipStream_t s, const GutParams& P, const GutProjected& proj, const float* density12, const float* sph,
-                          const GutGradSlots& slots, bool has_gdist, bool have_partials, float* g_rgb, const GutGradOut& g_out, float* g_sph,
-                          float* g_radiance, uint32_t first, uint32_t end) {
+                          const GutSplitSph& split, const GutGradSlots& slots, bool has_gdist, bool have_partials, float* g_rgb,
+                          const GutGradOut& g_out, float* g_sph, const GutSplitSphGrad& g_split, float* g_radiance, uint32_t first, uint32_t end) {
     // particles [first, end) (first a multiple of 128): everything, or one chunk of the pipelined exchange
     if (end > P.N) end = P.N;
     if (end <= first) return;
     const dim3 grid(div_up(end - first, 64)), block(256);  // four lanes per particle
     static const bool unfused = [] { const char* e = getenv("GRUT_GUT_UNFUSED_FINALIZE"); return e && e[0] == '1'; }();   // (A/B measurements)
+    if (!unfused && split.specular) {   // one kernel on the model's two SH tensors (fp32, 16 coefficients: the API's precondition)
+        if (has_gdist)
+            hipLaunchKernelGGL((gut_grad_gather_kernel<20, false, true, true>), grid, block, 0, s, P, proj, reinterpret_cast<const float4*>(density12),
+                               slots, have_partials ? 1 : 0, g_out, g_rgb, first, end, split.albedo, g_split.albedo, split.specular, g_split.specular);
+        else
+            hipLaunchKernelGGL((gut_grad_gather_kernel<16, false, true, true>), grid, block, 0, s, P, proj, reinterpret_cast<const float4*>(density12),
+                               slots, have_partials ? 1 : 0, g_out, g_rgb, first, end, split.albedo, g_split.albedo, split.specular, g_split.specular);
+        return;
+    }
     if (!unfused && !g_radiance && g_sph && P.ncoef == 16 && !P.sph_half) {   // one kernel: gather + projection backward
         if (has_gdist)
             hipLaunchKernelGGL((gut_grad_gather_kernel<20, false, true>), grid, block, 0, s, P, proj, reinterpret_cast<const float4*>(density12), slots,
@@ -1315,7 +1476,7 @@ void launch_grad_finalize(hipStream_t s, const GutParams& P, const GutProjected&
     else
         hipLaunchKernelGGL(gut_grad_gather_kernel<16>, grid, block, 0, s, P, proj, reinterpret_cast<const float4*>(density12), slots,
                            have_partials ? 1 : 0, g_out, g_rgb, first, end);
-    launch_project_bwd(s, P, proj, density12, sph, g_rgb, g_out, g_sph, g_radiance, first, end);
+    launch_project_bwd(s, P, proj, density12, sph, split, g_rgb, g_out, g_sph, g_split, g_radiance, first, end);
 }
 
 }  // namespace grut

@@ -48,6 +48,14 @@ def fused_activations_requested(conf) -> bool:
     return bool(_conf_get(_conf_get(conf, "render"), "fused_activations", False)) or bool(os.environ.get("GRUT_FUSED_ACTIVATIONS"))
 
 
+def split_sh_requested(conf) -> bool:
+    """`render.split_sh_features: true` (a key of this plugin, absent from the reference's configs) or GRUT_SPLIT_SH=1: hand the model's
+    two SH Parameters, features_albedo [N,3] and features_specular [N,45] (threedgrut/model/model.py:204-210), to the library where they
+    lie and get their two gradients back as contiguous tensors - no get_features() (the torch.cat of model.py:94-96), no [N,48] buffer,
+    no CatBackward slices."""
+    return bool(_conf_get(_conf_get(conf, "render"), "split_sh_features", False)) or bool(os.environ.get("GRUT_SPLIT_SH"))
+
+
 def has_standard_activations(gaussians) -> bool:
     """The model stores raw parameters and activates them with exactly the functions the fused kernels implement
     (threedgrut/model/model.py:237-241 with configs/base_gs.yaml:77-78; utils/misc.py:44-49)."""
@@ -163,6 +171,13 @@ class _GutNative:
         return f
 
     def trace(self, frame, particle_density, particle_sph, ray_ori, ray_dir):
+        return self._trace(frame, particle_density, (particle_sph,), ray_ori, ray_dir)
+
+    def trace_split(self, frame, particle_density, sph_albedo, sph_specular, ray_ori, ray_dir):
+        """gut_forward_split: the coefficients as the model's two tensors, [N,3] and [N,45], read where they lie."""
+        return self._trace(frame, particle_density, (sph_albedo, sph_specular), ray_ori, ray_dir)
+
+    def _trace(self, frame, particle_density, sph, ray_ori, ray_dir):
         dev = ray_ori.device
         H, W = frame.height, frame.width
         N = frame.num_particles
@@ -190,9 +205,9 @@ class _GutNative:
         else:
             out_feat, out_opa = _uninitialised((H, W, 3), **opts), _uninitialised((H, W, 1), **opts)
         frame.out_features, frame.out_opacity = (None, None) if half_out else (out_feat.data_ptr(), out_opa.data_ptr())
-        _abi.check(self.lib.gut_forward(self.handle, _stream_ptr(dev), C.byref(frame), _ptr(particle_density), _ptr(particle_sph),
-                                        _ptr(ray_ori), _ptr(ray_dir), _ptr(out_fd), _ptr(out_dist), _ptr(out_cnt), _ptr(vis_i32)),
-                   "gut_forward")
+        fn, name = (self.lib.gut_forward, "gut_forward") if len(sph) == 1 else (self.lib.gut_forward_split, "gut_forward_split")
+        _abi.check(fn(self.handle, _stream_ptr(dev), C.byref(frame), _ptr(particle_density), *map(_ptr, sph),
+                      _ptr(ray_ori), _ptr(ray_dir), _ptr(out_fd), _ptr(out_dist), _ptr(out_cnt), _ptr(vis_i32)), name)
         # the reference returns a float tensor holding the int bit pattern (splatRaster.cpp:215,249); consumers call .bool()
         frame.out_features, frame.out_opacity = None, None   # the frame outlives this call in the autograd context
         if half_out:
@@ -251,6 +266,26 @@ class _GutNative:
                                                   _ptr(ray_ori), _ptr(ray_dir), _ptr(fd), _ptr(dist), _ptr(g_dist), C.byref(io), _ptr(g_sph)),
                    "gut_backward_unpacked")
         return g_pos, g_dns, g_rot, g_scl, g_sph
+
+    def trace_bwd_split(self, frame, particle_density, sph_albedo, sph_specular, ray_ori, ray_dir, fd, g_fd, dist, g_dist):
+        """gut_backward_split: (packed gradient [N,12], albedo gradient [N,3], specular gradient [N,45]), all fully written."""
+        g_density, g_albedo, g_specular = torch.empty_like(particle_density), torch.empty_like(sph_albedo), torch.empty_like(sph_specular)
+        _abi.check(self.lib.gut_backward_split(self.handle, _stream_ptr(ray_ori.device), C.byref(frame), _ptr(particle_density), _ptr(sph_albedo),
+                                               _ptr(sph_specular), _ptr(ray_ori), _ptr(ray_dir), _ptr(fd), _ptr(g_fd), _ptr(dist), _ptr(g_dist),
+                                               _ptr(g_density), _ptr(g_albedo), _ptr(g_specular)), "gut_backward_split")
+        return g_density, g_albedo, g_specular
+
+    def trace_bwd_unpacked_split(self, frame, particle_density, sph_albedo, sph_specular, ray_ori, ray_dir, fd, g_feat, g_opa, dist, g_dist):
+        """gut_backward_unpacked_split: trace_bwd_unpacked with the SH gradient as the model's two tensor shapes."""
+        n = particle_density.shape[0]
+        opts = dict(dtype=torch.float32, device=ray_ori.device)
+        g_pos, g_dns, g_rot, g_scl = torch.empty((n, 3), **opts), torch.empty((n, 1), **opts), torch.empty((n, 4), **opts), torch.empty((n, 3), **opts)
+        g_albedo, g_specular = torch.empty_like(sph_albedo), torch.empty_like(sph_specular)
+        io = _abi.GutGradIO(_ptr(g_feat), _ptr(g_opa), _ptr(g_pos), _ptr(g_dns), _ptr(g_rot), _ptr(g_scl))
+        _abi.check(self.lib.gut_backward_unpacked_split(self.handle, _stream_ptr(ray_ori.device), C.byref(frame), _ptr(particle_density),
+                                                        _ptr(sph_albedo), _ptr(sph_specular), _ptr(ray_ori), _ptr(ray_dir), _ptr(fd), _ptr(dist),
+                                                        _ptr(g_dist), C.byref(io), _ptr(g_albedo), _ptr(g_specular)), "gut_backward_unpacked_split")
+        return g_pos, g_dns, g_rot, g_scl, g_albedo, g_specular
 
     def trace_bwd_factored(self, frame, particle_density, particle_sph, ray_ori, ray_dir, fd, g_fd, dist, g_dist):
         """gut_backward_factored: (packed gradient [N,12], view factor [N+1,3]) — see 3dgrut_amd/dp.py."""
@@ -417,11 +452,55 @@ class Tracer:
             g_pos, g_dns, g_rot, g_scl = _abi.unpack_particle_grads(g_density)
             return None, None, None, None, g_pos, g_rot, g_scl, g_dns, g_sph, None, None
 
+    class _AutogradSplit(torch.autograd.Function):
+        """_Autograd with the SH coefficients as the model's two leaves (split_sh_requested): features_albedo [N,3] and features_specular
+        [N,45] go to the library as they are and their gradients come back as two contiguous tensors.  Only taken without a gradient
+        exchange, with k_buffer_size 0, fp32 coefficients and SH degree 3 (Tracer._split_sh_tensors)."""
+
+        @staticmethod
+        def forward(ctx, native, frame, ray_ori, ray_dir, mog_pos, mog_rot, mog_scl, mog_dns, sph_albedo, sph_specular, raw=False):
+            if raw:
+                particle_density = _abi.activate_pack(mog_pos, mog_dns, mog_rot, mog_scl)
+            else:
+                particle_density = _abi.pack_particles(mog_pos, mog_dns, mog_rot, mog_scl)
+            ctx.raw = (mog_dns, mog_rot, mog_scl) if raw else None
+            fd, dist, cnt, vis, feat, opa = native.trace_split(frame, particle_density, sph_albedo, sph_specular, ray_ori, ray_dir)
+            ctx.save_for_backward(ray_ori, ray_dir, fd, dist, particle_density, sph_albedo, sph_specular)
+            ctx.native, ctx.frame = native, frame
+            feat = feat.unsqueeze(0)
+            opa = opa.unsqueeze(0)
+            ctx.mark_non_differentiable(cnt, vis)
+            ctx.set_materialize_grads(False)
+            return feat, opa, dist, cnt, vis
+
+        @staticmethod
+        def backward(ctx, g_feat, g_opa, g_dist, _g_cnt, _g_vis):
+            ray_ori, ray_dir, fd, dist, particle_density, sph_albedo, sph_specular = ctx.saved_tensors
+            H, W = fd.shape[0], fd.shape[1]
+            g_dist = None if g_dist is None else g_dist.contiguous()
+            if ctx.raw is None:
+                g_pos, g_dns, g_rot, g_scl, g_albedo, g_specular = ctx.native.trace_bwd_unpacked_split(
+                    ctx.frame, particle_density, sph_albedo, sph_specular, ray_ori, ray_dir, fd,
+                    None if g_feat is None else g_feat.reshape(H, W, 3).contiguous(), None if g_opa is None else g_opa.reshape(H, W, 1).contiguous(),
+                    dist, g_dist)
+                return None, None, None, None, g_pos, g_rot, g_scl, g_dns, g_albedo, g_specular, None
+            # fused activations: the packed gradient goes through the activations' chain rule, as in _Autograd
+            g_feat = fd.new_zeros((H, W, 3)) if g_feat is None else g_feat.reshape(H, W, 3)
+            g_opa = fd.new_zeros((H, W, 1)) if g_opa is None else g_opa.reshape(H, W, 1)
+            g_fd = torch.cat([g_feat, g_opa], dim=-1)
+            g_density, g_albedo, g_specular = ctx.native.trace_bwd_split(ctx.frame, particle_density, sph_albedo, sph_specular, ray_ori, ray_dir,
+                                                                         fd, g_fd, dist, g_dist)
+            g_pos, g_dns, g_rot, g_scl = _abi.activate_pack_backward(*ctx.raw, g_density)
+            return None, None, None, None, g_pos, g_rot, g_scl, g_dns, g_albedo, g_specular, None
+
     def __init__(self, conf):
         self.device = "cuda"
         self.conf = conf
         self.tracer_wrapper = _GutNative(gut_config_from_conf(conf))   # raises without a ROCm GPU: there is no CPU fallback
         self._fused_activations = fused_activations_requested(conf)
+        self._split_sh = split_sh_requested(conf)
+        # which SH path the render() calls took: the two leaves in place, or get_features() (the model's torch.cat)
+        self.stats_split = {"split_calls": 0, "cat_calls": 0}
         # set to a 3dgrut_amd.dp.FactoredGradientExchange to have the backward exchange its gradients across ranks (one view
         # per GPU); None (default) = single-GPU behaviour, exactly the reference's
         self.gradient_exchange = None
@@ -441,6 +520,21 @@ class Tracer:
             self._normals_key = key
         return self._normals
 
+    def _split_sh_tensors(self, gaussians, device):
+        """(features_albedo, features_specular) when this call can hand them to the split entry points, else None (= get_features())."""
+        c = self.tracer_wrapper.cfg
+        if (not self._split_sh or self.gradient_exchange is not None or c.feature_transform_type or c.particle_feature_half
+                or int(c.particle_radiance_sph_degree) != 3 or int(c.k_buffer_size) != 0):
+            return None
+        n = int(gaussians.num_gaussians)
+        albedo, specular = getattr(gaussians, "features_albedo", None), getattr(gaussians, "features_specular", None)
+        for t, cols in ((albedo, 3), (specular, 45)):
+            # (the rays' device: a ROCm device whenever the real library is underneath; 16 bytes: the entry points' alignment rule)
+            if (n == 0 or not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != device or tuple(t.shape) != (n, cols)
+                    or not t.is_contiguous() or t.data_ptr() % 16):
+                return None
+        return albedo, specular
+
     def render(self, gaussians, gpu_batch, train=False, frame_id=0):
         rays_o = gpu_batch.rays_ori if not isinstance(gpu_batch, dict) else gpu_batch["rays_ori"]
         rays_d = gpu_batch.rays_dir if not isinstance(gpu_batch, dict) else gpu_batch["rays_dir"]
@@ -458,6 +552,21 @@ class Tracer:
             frame.device_T_to_world = t0.data_ptr()
             frame.device_T_to_world_end = None if t1 is None else t1.data_ptr()
             frame._keepalive = (t0, t1)
+        split = self._split_sh_tensors(gaussians, rays_o.device)
+        if split is not None:   # the model's two SH tensors in place: get_features() (model.py:94-96) is not called at all
+            if getattr(gaussians, "ray_feature_dim", 3) != 3:
+                raise NotImplementedError("3dgrut_amd: only SH radiance features (ray_feature_dim = 3) are supported")
+            self.stats_split["split_calls"] += 1
+            raw = self._fused_activations and has_standard_activations(gaussians)
+            pred_features, pred_opacity, pred_dist, hits_count, mog_visibility = Tracer._AutogradSplit.apply(
+                native, frame, rays_o.contiguous().float(), rays_d.contiguous().float(), gaussians.positions.contiguous(),
+                (gaussians.rotation if raw else gaussians.get_rotation()).contiguous(), (gaussians.scale if raw else gaussians.get_scale()).contiguous(),
+                (gaussians.density if raw else gaussians.get_density()).contiguous(), split[0], split[1], raw)
+            timings = native.collect_times()
+            return {"pred_features": pred_features, "pred_opacity": pred_opacity, "pred_dist": pred_dist.unsqueeze(0),
+                    "pred_normals": self._constant_normals(pred_features), "hits_count": hits_count.unsqueeze(0),
+                    "frame_time_ms": timings["forward_render"] if "forward_render" in timings else 0.0, "mog_visibility": mog_visibility}
+        self.stats_split["cat_calls"] += 1
         feats = gaussians.get_features()
         if native.cfg.feature_transform_type:   # neural harmonic features (K = 0)
             if feats.shape[1] != native.cfg.particle_feature_dim:

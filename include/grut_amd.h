@@ -207,6 +207,43 @@ int gut_backward_unpacked(GutHandle* handle, void* stream, const GutFrame* frame
                           const void* feat_density, const float* hit_distance, const float* grad_hit_distance,
                           const GutGradIO* io, float* grad_particle_sph);
 
+/* ---- the model's two SH tensors read in place (new surface) ----------------------------------------------------------------------
+ * Every SH configuration of the reference keeps the radiance coefficients in two Parameters, features_albedo [N,3] and
+ * features_specular [N,45] (threedgrut/model/model.py:204-210), and joins them with torch.cat on every get_features() call
+ * (model.py:94-96); autograd then slices grad_particle_sph [N,48] apart again and clones both slices.  The three entry points below
+ * are gut_forward, gut_backward and gut_backward_unpacked with that pair in place of particle_sph and the pair of their gradients in
+ * place of grad_particle_sph (they replace the get_features() call at the top of 3dgrut_amd/gut_tracer.py's Tracer.render and the
+ * single g_sph tensor of its autograd Function): virtual float e of particle i's 48-float row is sph_albedo[3 i + e] for e < 3 and
+ * sph_specular[45 i + e - 3] otherwise, for the coefficients and for their gradients.  The arithmetic and its order are the twins':
+ * every output equals theirs bit for bit.
+ *   sph_albedo [N,3] f32, sph_specular [N,45] f32: read only, and only rows of the arrays (specular rows are 180 bytes: row i begins
+ *     on a 4-byte boundary only, and nothing is read beyond float 45 N);
+ *   grad_sph_albedo [N,3] f32, grad_sph_specular [N,45] f32: fully overwritten - zeros for particles without tiles and for the
+ *     coefficients beyond 3 (n_active_features + 1)^2 - with no atomics: two calls give equal bits.
+ * Alignment: the four base pointers must be 16-byte aligned (GRUT_ERR_BAD_INPUT otherwise; any allocator's blocks are).
+ * Accepted configurations: SH radiance (feature_transform_type 0) with particle_radiance_sph_degree 3, fp32 coefficients
+ * (particle_feature_half 0) and k_buffer_size 0; anything else is GRUT_ERR_UNSUPPORTED with the reason in grut_last_error().  A NULL
+ * among the four pointers is GRUT_ERR_BAD_INPUT.  Both errors come before any launch and leave the handle's forward context alone.
+ * Forward context: as for the twins (same handle, stream, frame_id, density and ray pointers, else GRUT_ERR_NOT_READY); the SH
+ * pointers are not part of it, and a forward of one kind may be followed by a backward of the other.
+ * GRUT_GUT_UNFUSED_FINALIZE=1 selects the two-kernel gradient finalisation here as it does for the twins. */
+int gut_forward_split(GutHandle* handle, void* stream, const GutFrame* frame,
+                      const float* particle_density, const float* sph_albedo, const float* sph_specular,
+                      const float* ray_origin, const float* ray_direction,
+                      void* out_feat_density, float* out_hit_distance,
+                      float* out_hit_count, int32_t* out_visibility);
+int gut_backward_split(GutHandle* handle, void* stream, const GutFrame* frame,
+                       const float* particle_density, const float* sph_albedo, const float* sph_specular,
+                       const float* ray_origin, const float* ray_direction,
+                       const void* feat_density, const float* grad_feat_density,
+                       const float* hit_distance, const float* grad_hit_distance,
+                       float* grad_particle_density, float* grad_sph_albedo, float* grad_sph_specular);
+int gut_backward_unpacked_split(GutHandle* handle, void* stream, const GutFrame* frame,
+                                const float* particle_density, const float* sph_albedo, const float* sph_specular,
+                                const float* ray_origin, const float* ray_direction,
+                                const void* feat_density, const float* hit_distance, const float* grad_hit_distance,
+                                const GutGradIO* io, float* grad_sph_albedo, float* grad_sph_specular);
+
 /* ---- view-sharded data parallelism: the radiance gradient in factored form (new surface; the reference is
  * single-GPU) ------------------------------------------------------------------------------------------------------------------
  * With one view per GPU, the gradient exchange of a step is dominated by grad_particle_sph: 3*(deg+1)^2 floats per particle
