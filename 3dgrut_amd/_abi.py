@@ -176,6 +176,7 @@ EXPORTED_SYMBOLS = [
     "grt_create", "grt_destroy", "grt_build_bvh", "grt_forward", "grt_backward", "grt_timings", "grt_stats", "grt_debug_fetch_work",
     "grt_debug_forward_hits", "grt_debug_fetch_instances", "grt_debug_fetch_custom_boxes", "grt_debug_fetch_lists", "grt_debug_backward_signature", "grt_build_mesh_bvh", "grt_trace_hybrid",
     "grut_selective_adam_update", "grut_pack_particles", "grut_unpack_particle_grads", "grut_activate_pack", "grut_activate_pack_backward",
+    "grut_reg_partials", "grut_reg_forward", "grut_reg_backward",
     "grut_mcmc_relocation", "grut_mcmc_perturb",
     "grut_mcmc_classify", "grut_mcmc_classify_scratch_bytes", "grut_mcmc_sample_plan", "grut_mcmc_relocate_rows", "grut_mcmc_append_rows",
     "grut_densify_accumulate", "grut_relayout_scan", "grut_relayout_scratch_bytes", "grut_relayout_rows", "grut_split_tail",
@@ -305,6 +306,13 @@ def _declare(lib):
     lib.grut_activate_pack.restype = C.c_int
     lib.grut_activate_pack_backward.argtypes = [vp, C.c_uint32] + [fp] * 8
     lib.grut_activate_pack_backward.restype = C.c_int
+    # stream, N, raw_density / raw_scale (either may be NULL), then partials, out [2] / grad_out [2] (device), the two gradients (NULL: not wanted)
+    lib.grut_reg_partials.argtypes = [C.c_uint32]
+    lib.grut_reg_partials.restype = C.c_uint32
+    lib.grut_reg_forward.argtypes = [vp, C.c_uint32, fp, fp, fp, fp]
+    lib.grut_reg_forward.restype = C.c_int
+    lib.grut_reg_backward.argtypes = [vp, C.c_uint32, fp, fp, fp, fp, fp]
+    lib.grut_reg_backward.restype = C.c_int
     lib.grut_mcmc_relocation.argtypes = [vp, C.c_uint32, fp, fp, ip, fp, C.c_int, fp, fp]
     lib.grut_mcmc_relocation.restype = C.c_int
     lib.grut_mcmc_perturb.argtypes = [vp, C.c_uint32, fp, fp, fp, fp, fp, C.c_float, C.c_float, C.c_int]

@@ -21,7 +21,7 @@ import types
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _abi
+from . import _abi, regularizers
 
 SHIM_MODULE = "fused_ssim"
 WINDOW = 11
@@ -293,7 +293,8 @@ def install_fused_losses():
     """Opt-in: replace threedgrut.trainer.Trainer3DGRUT.get_losses IN PLACE on the class (so it holds however train.py imported the class)
     with a method that makes one photometric_loss call for the masking, L1, L2 and SSIM of trainer.py:687-720 and returns the reference's
     dict: the same six keys, the same weighting, torch.zeros(1) for disabled terms, the opacity and scale regularisers in torch as the
-    reference has them.  outputs["pred_features"] is not replaced.  Whenever a precondition of the fused call does not hold (pred or gt
+    reference has them (in one HIP call after regularizers.install_fused_regularizers(), which is off by default).
+    outputs["pred_features"] is not replaced.  Whenever a precondition of the fused call does not hold (pred or gt
     not an fp32 CUDA [B, H, W, C] tensor, C > 4, B * C over the kernels' limit, H or W below 11 with SSIM on, a mask that is not an fp32
     [B, H, W, 1] tensor on that device, or no image term enabled) the reference's own method runs.  Returns the new method;
     calling it again returns the same one."""
@@ -313,12 +314,15 @@ def install_fused_losses():
         loss_l1, lambda_l1 = (l1, conf.lambda_l1) if use_l1 else (torch.zeros(1, device=self.device), 0.0)
         loss_l2, lambda_l2 = (l2, conf.lambda_l2) if use_l2 else (torch.zeros(1, device=self.device), 0.0)
         loss_ssim, lambda_ssim = (1.0 - ssim_mean, conf.lambda_ssim) if use_ssim else (torch.zeros(1, device=self.device), 0.0)
+        means = None   # regularizers.install_fused_regularizers(): both means in one HIP call; None where the two torch lines have to run
+        if regularizers.enabled() and not self._in_color_refine and (conf.use_opacity or conf.use_scale):
+            means = regularizers.trainer_means(self.model, bool(conf.use_opacity), bool(conf.use_scale))
         loss_opacity, lambda_opacity = torch.zeros(1, device=self.device), 0.0
         if conf.use_opacity and not self._in_color_refine:
-            loss_opacity, lambda_opacity = torch.abs(self.model.get_density()).mean(), conf.lambda_opacity
+            loss_opacity, lambda_opacity = torch.abs(self.model.get_density()).mean() if means is None else means[0], conf.lambda_opacity
         loss_scale, lambda_scale = torch.zeros(1, device=self.device), 0.0
         if conf.use_scale and not self._in_color_refine:
-            loss_scale, lambda_scale = torch.abs(self.model.get_scale()).mean(), conf.lambda_scale
+            loss_scale, lambda_scale = torch.abs(self.model.get_scale()).mean() if means is None else means[1], conf.lambda_scale
 
         loss = lambda_l1 * loss_l1 + lambda_ssim * loss_ssim + lambda_opacity * loss_opacity + lambda_scale * loss_scale
         return dict(total_loss=loss, l1_loss=lambda_l1 * loss_l1, l2_loss=lambda_l2 * loss_l2, ssim_loss=lambda_ssim * loss_ssim,

@@ -587,6 +587,38 @@ int grut_activate_pack_backward(void* stream, uint32_t num_particles, const floa
                                 const float* raw_scale, const float* grad_particle_density, float* grad_positions,
                                 float* grad_raw_density, float* grad_raw_rotation, float* grad_raw_scale);
 
+/* ---- opacity and scale regularisers (threedgrut/trainer.py:722-736, on in configs/base_mcmc.yaml) ------------ */
+/* The two means Trainer3DGRUT.get_losses takes of the ACTIVATED parameters, from the raw tensors:
+ *   out[0] = 1/N  sum_i  sigmoid(raw_density[i])          torch.abs(model.get_density()).mean()
+ *   out[1] = 1/3N sum_ij exp(raw_scale[i][j])             torch.abs(model.get_scale()).mean()
+ * Both activations are non-negative, so the reference's abs is the identity and is not evaluated.  Each activation is evaluated in
+ * double and rounded to fp32 once: the expf that grut_activate_pack renders with was measured up to 11 ulp off on gfx950, which is
+ * more than the bounds of these sums and gradients allow; the value rendered is within those 11 ulp of the value regularised.
+ * A NULL input skips its term and its slot of `out` is +0.0f; at least one input is needed.
+ * Summation, all fp32 and in one fixed order: a lane sums its float4 as (x + y) + (z + w) and carries the trips of its grid-stride
+ * loop in a compensated (Kahan) sum; 64 lanes and then the 4 waves of a block are added as balanced binary trees; a second launch
+ * of one block adds the block partials in index order, again as a balanced tree, and divides.  The non-zero leaves fill a prefix of
+ * every tree, so no term passes more than min(ceil(log2(count)), 22) roundings, whatever N is.  No atomics, no allocation, no
+ * synchronisation, two launches on `stream`, a grid that depends on N only: two calls on the same input are bitwise equal.
+ * partials: grut_reg_partials(N) floats of scratch that belong to the caller (two per block, at most 8 KiB); nothing has to be
+ * zeroed.  grut_reg_partials is host arithmetic and returns 0 where the forward call would refuse N.
+ *
+ * Backward, one launch, grad_out [2] read on the device:
+ *   grad_raw_density[i]  = grad_out[0] / N  * s (1 - s),  s = sigmoid(raw_density[i])
+ *   grad_raw_scale[i][j] = grad_out[1] / 3N * exp(raw_scale[i][j])
+ * s (1 - s) is evaluated as e / (1 + e)^2 with e = exp(-|x|), which keeps its leading digits where s rounds to 1; every element
+ * is computed in double and rounded once.  Each output is
+ * overwritten completely.  A NULL gradient pointer means that term is not wanted (its slot of grad_out is not read); a gradient
+ * whose input is NULL is an error, and so are two NULL gradients.  Where an activation underflows to exactly 0 the reference's
+ * abs passes sign(0) = 0 and these formulas give 0 as well: no special case.
+ * Every non-NULL tensor base must be 16-byte aligned (the flat [N] and [3N] arrays move as float4; one may straddle rows of
+ * raw_scale).  GRUT_ERR_BAD_INPUT, before any launch and with the argument named by grut_last_error: N == 0, 3N >= 2^32, both
+ * inputs NULL, a NULL out / partials / grad_out, a misaligned base. */
+uint32_t grut_reg_partials(uint32_t num_particles);
+int grut_reg_forward(void* stream, uint32_t num_particles, const float* raw_density, const float* raw_scale, float* partials, float* out);
+int grut_reg_backward(void* stream, uint32_t num_particles, const float* raw_density, const float* raw_scale, const float* grad_out,
+                      float* grad_raw_density, float* grad_raw_scale);
+
 /* ---- MCMC densification strategy (threedgrut/strategy/mcmc.py) ---------------------------------------------- */
 /* Replaces compute_relocation_kernel (threedgrut/strategy/src/gaussian_mcmc.cu:36-66, host side :70-92), one lane per sampled
  * Gaussian: new_opacities[i] = 1 - (1 - opacities[i])^(1/n), new_scales[i] = opacities[i] / D * scales[i] with
