@@ -107,8 +107,9 @@ static int grt_validate(const GrtConfig& c) {
         GRUT_REQUIRE(nf >= 1 && nr >= 1 && nr <= 32, "ray feature dim %d: 1..32 supported", nr);
         GRUT_REQUIRE(c.particle_feature_dim + 11 <= 64, "particle_feature_dim %d: at most 53 (one wave carries a hit's gradient words)", c.particle_feature_dim);
     }
-    if (c.pipeline_type != GRUT_PIPELINE_REFERENCE) {
-        GRUT_REQUIRE(c.pipeline_type == GRUT_PIPELINE_BARYCENTRIC_SURFELS, "pipeline_type %d: reference (0) or barycentricSurfels (1)", c.pipeline_type);
+    // (GRUT_PIPELINE_REFERENCE_SLANG: the kernels of the reference pipeline; custom primitives take the Slang test's unsigned distance, RayW::absdist)
+    if (c.pipeline_type != GRUT_PIPELINE_REFERENCE && c.pipeline_type != GRUT_PIPELINE_REFERENCE_SLANG) {
+        GRUT_REQUIRE(c.pipeline_type == GRUT_PIPELINE_BARYCENTRIC_SURFELS, "pipeline_type %d: reference (0), barycentricSurfels (1) or referenceSlang (2)", c.pipeline_type);
         // (barycentricSurfelsOptix.cu reads the hit triangle's barycentrics and the trisurfel kernel's {normal, density} rows, optixTracer.cpp:735-748)
         GRUT_REQUIRE(c.primitive_type == GRUT_PRIM_TRISURFEL, "pipeline_type barycentricSurfels: primitive_type must be trisurfel");
         GRUT_REQUIRE(c.feature_transform_type == 0 && !c.particle_feature_half && !c.feature_output_half, "pipeline_type barycentricSurfels: fp32 SH radiance only");
@@ -126,6 +127,7 @@ static GrtTraceParams trace_params(const GrtHandle* h, const GrtFrame& f) {
     P.degree = h->cfg.particle_kernel_degree;
     P.prim = h->cfg.primitive_type;
     P.bary = h->cfg.pipeline_type == GRUT_PIPELINE_BARYCENTRIC_SURFELS;
+    P.slang = h->cfg.pipeline_type == GRUT_PIPELINE_REFERENCE_SLANG;
     P.clamping = h->cfg.particle_kernel_density_clamping;
     P.box8 = h->cfg.primitive_type == GRUT_PRIM_CUSTOM ? h->box8.as<float>() : nullptr;
     P.ncoef = (h->cfg.particle_radiance_sph_degree + 1) * (h->cfg.particle_radiance_sph_degree + 1);

@@ -44,6 +44,7 @@ struct GrtTraceParams {
     int W, H;
     int prim;                 // GrtConfig::primitive_type (GRUT_PRIM_*): which candidate test a (ray, particle) pair takes
     int bary;                 // GrtConfig::pipeline_type == GRUT_PIPELINE_BARYCENTRIC_SURFELS: ten hits per trace, response from the plane crossing (forward only)
+    int slang;                // GrtConfig::pipeline_type == GRUT_PIPELINE_REFERENCE_SLANG: custom primitives take the Slang test's unsigned hit distance (RayW::absdist)
     int clamping;             // GrtConfig::particle_kernel_density_clamping (the surfel pipeline's scaled response needs it per hit)
     const float* box8;        // GRUT_PRIM_CUSTOM: [N,8] {world box, kernelScale^2, 0} of the proxy kernel (null otherwise)
     float ray_to_world[12];

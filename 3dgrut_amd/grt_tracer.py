@@ -35,10 +35,15 @@ def grt_config_from_conf(conf) -> _abi.GrtConfig:
     # backward_pipeline_type referenceSlangBwd); SH radiance on the `reference` pipelines
     nht = nht_config_from_conf(conf, cfg)
     pipeline = _conf_get(render, "pipeline_type", "reference")
-    # `referenceSlang` with SH radiance: the Slang programs (referenceSlangOptix.cu + gaussianParticles.slang / shRadiativeParticles.slang)
-    # integrate the same function as the hand-written ones — same hit test, response, alpha clamps, weights and radiance — in another
-    # rounding order; both names are served by the same kernels (the SH path is pinned by the `reference` programs only)
+    # `referenceSlang` (SH radiance or features): the Slang programs (referenceSlangOptix.cu + gaussianParticles.slang / shRadiativeParticles.slang)
+    # integrate the same function as the hand-written ones — same response, alpha clamps, weights and radiance — and run on the same kernels,
+    # which carry the flavour (GrtConfig.pipeline_type = GRUT_PIPELINE_REFERENCE_SLANG) because ONE candidate test differs: with
+    # primitive_type custom the Slang intersection program reports an UNSIGNED hit distance (particleDensityHitCustom,
+    # gaussianParticles.slang:489-523), so a particle whose point of maximum response lies behind the ray origin is a candidate there and not
+    # under `reference`.  Every other primitive: the two programs' outputs are bit-equal (tests/golden/grt_trace_slang_sh_prims.npz)
     allowed = _SUPPORTED_PIPELINES
+    if pipeline == "referenceSlang":
+        cfg.pipeline_type = 2
     # `barycentricSurfels` (barycentricSurfelsOptix.cu, round 6): the surfel forward pipeline - trisurfel proxies, ten hits per trace, the
     # response from the hit triangle's barycentrics.  FORWARD ONLY: the reference ships no backward program for it (the constructor's default
     # backward name `barycentricSurfelsBwd` has no file, optixTracer.cpp:311-314); backward() raises here
@@ -59,6 +64,20 @@ def grt_config_from_conf(conf) -> _abi.GrtConfig:
     prim = _conf_get(render, "primitive_type", "instances")
     if prim not in _abi.GRT_PRIMITIVES:
         raise NotImplementedError(f"3dgrut_amd: render.primitive_type={prim!r} is not supported (provided: {tuple(_abi.GRT_PRIMITIVES)})")
+    if prim == "custom" and (pipeline == "referenceSlang") != (bwd_pipeline == "referenceSlangBwd"):
+        # (one handle, one convention: the backward differentiates the hits the forward processed)
+        raise NotImplementedError(f"3dgrut_amd: render.pipeline_type={pipeline!r} with render.backward_pipeline_type={bwd_pipeline!r} is not provided "
+                                  "with primitive_type custom: the Slang programs take the unsigned hit distance (particleDensityHitCustom), the "
+                                  "hand-written ones the signed one (intersectCustomParticle), so the two passes would trace different candidate sets")
+    if pipeline == "referenceSlang" and prim == "trisurfel" and not nht:
+        # every other primitive: the Slang forward program's outputs equal the hand-written program's bit for bit (hit distance to 1e-6) on the
+        # golden scene, so one set of kernels serves both.  Not so here: the Slang surfel mode (GAUSSIAN_PARTICLE_SURFEL: scale.z = 1e-6,
+        # gaussianParticles.slang:49-51, 125-127) is not restated in the host stand-in the goldens are made with, and
+        # the program built from it differs from the hand-written one that these kernels follow
+        raise NotImplementedError("3dgrut_amd: render.pipeline_type='referenceSlang' with primitive_type trisurfel and SH radiance is not provided: on the "
+                                  "24x16 golden scene the Slang forward program (built from the host stand-in, which has no surfel mode) and the hand-written "
+                                  "program differ in the accepted-hit count on 315 of 384 rays (6019 / 6419 hits), by 0.52 in radiance, 0.48 in opacity and on "
+                                  "33 visibility flags (tests/golden/grt_trace_slang_sh_prims.npz); use pipeline_type 'reference'")
     if nht and prim == "trisurfel":
         # (the feature path walks the trace kernel's hit log and evaluates the features at each hit's canonical intersection: it does not care
         # which candidate test ordered the log - instances, the closed mesh proxies, trihexa and sphere (round 6: proxy -> particle at the

@@ -386,15 +386,20 @@ typedef struct GrtConfig {
      * (gaussianParticles.cuh:407-441): the instances' hit point, offered to the rays that cross the world box, accepted within 3 sigma.
      * The open meshes GRUT_PRIM_TRISURFEL / GRUT_PRIM_TRIHEXA and the enclosing spheres GRUT_PRIM_SPHERE: below. */
     int32_t primitive_type;
-    /* render.pipeline_type (optixTracer.cpp:246-318: the forward program's file).  GRUT_PIPELINE_REFERENCE: referenceOptix.cu (and the Slang
-     * pipelines, served by the same kernels).  GRUT_PIPELINE_BARYCENTRIC_SURFELS: barycentricSurfelsOptix.cu - FORWARD ONLY (the reference ships
+    /* render.pipeline_type (optixTracer.cpp:246-318: the forward program's file).  GRUT_PIPELINE_REFERENCE: referenceOptix.cu.
+     * GRUT_PIPELINE_REFERENCE_SLANG: referenceSlangOptix.cu (SH radiance or neural harmonic features).  The Slang programs integrate the same
+     * function as the hand-written ones and run on the same kernels, with ONE difference in the candidate test: for GRUT_PRIM_CUSTOM the Slang
+     * intersection program (particleDensityHitCustom, gaussianParticles.slang:489-523) reports the UNSIGNED distance of the point of maximum
+     * response, so a particle whose maximum lies behind the ray origin is a candidate there and not under GRUT_PIPELINE_REFERENCE (forward and
+     * backward alike).  Every other primitive: bit-equal program outputs (tests/golden/grt_trace_slang_sh_prims.npz).
+     * GRUT_PIPELINE_BARYCENTRIC_SURFELS: barycentricSurfelsOptix.cu - FORWARD ONLY (the reference ships
      * no backward program for it): trisurfel proxies (primitive_type must be GRUT_PRIM_TRISURFEL), ten hits per trace, the response evaluated
      * from the squared distance of the ray's crossing of the surfel's plane in the proxy frame (the hit triangle's barycentrics) with the
      * kernel-scaled minimum response, depth from the triangle hit distances, normals from the surfel's plane.  grt_backward returns
      * GRUT_ERR_UNSUPPORTED. */
     int32_t pipeline_type;
 } GrtConfig;
-enum { GRUT_PIPELINE_REFERENCE = 0, GRUT_PIPELINE_BARYCENTRIC_SURFELS = 1 };
+enum { GRUT_PIPELINE_REFERENCE = 0, GRUT_PIPELINE_BARYCENTRIC_SURFELS = 1, GRUT_PIPELINE_REFERENCE_SLANG = 2 };
 enum { GRUT_PRIM_INSTANCES = 0, GRUT_PRIM_ICOSAHEDRON = 1, GRUT_PRIM_OCTAHEDRON = 2, GRUT_PRIM_TETRAHEDRON = 3, GRUT_PRIM_DIAMOND = 4, GRUT_PRIM_CUSTOM = 5,
        /* trisurfel (particlePrimitives.cu:155-205): two triangles per particle = the rhombus |x| + |y| <= sqrt 2 of the proxy's z = 0 plane, traced
         * WITHOUT face culling (referenceOptix.cu:62); the hit is the ray's crossing of that plane and the per-hit math takes its

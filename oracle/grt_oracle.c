@@ -43,10 +43,11 @@ real orc_grt_kernel_scale(real density, real min_response, int clamping, real de
  * A process-wide setting of this test library (the entry points that take a GrtConfig set it from cfg->primitive_type). */
 #include "orc_polyhedra.h"
 static int g_prim = 0;
-/* custom primitives under the SLANG pipelines (neural harmonic features): particleDensityHitCustom (gaussianParticles.slang:489-523) reports
+/* custom primitives under the SLANG pipelines (cfg->pipeline_type GRUT_PIPELINE_REFERENCE_SLANG with SH radiance, and every neural-harmonic-feature
+ * entry point): particleDensityHitCustom (gaussianParticles.slang:489-523) reports
  * canonicalRayDistance - the UNSIGNED distance of the maximum-response point - where intersectCustomParticle (gaussianParticles.cuh:407-441)
  * reports it with the sign of the ray parameter: a particle whose maximum lies BEHIND the ray origin is a candidate of the Slang pipeline.
- * Set by the feature entry points, cleared by every other one. */
+ * Set by the feature entry points and by orc_grt_trace_fwd / orc_grt_trace_bwd for the Slang pipeline, cleared by every other one. */
 static int g_custom_abs = 0;
 void orc_grt_set_primitive(int prim) { g_prim = prim; g_custom_abs = 0; }
 /* GRUT_PRIM_CUSTOM (render.primitive_type custom): per particle {world box min, max, kernelScale^2, 0} - orc_grt_custom_boxes fills it, the
@@ -698,6 +699,7 @@ int orc_grt_trace_fwd(const GrtConfig* cfg, uint32_t N, const real* density12, c
                       const real* ray_d, real* out_rad, real* out_dns, real* out_hit2, real* out_nrm, real* out_cnt,
                       int32_t* visibility, uint32_t* dbg_ids, uint32_t* dbg_count, uint32_t dbg_cap) {
     orc_grt_set_primitive(cfg->primitive_type);
+    g_custom_abs = cfg->primitive_type == 5 && cfg->pipeline_type == GRUT_PIPELINE_REFERENCE_SLANG;
     if (cfg->pipeline_type == GRUT_PIPELINE_BARYCENTRIC_SURFELS)
         return cfg->primitive_type == 6 ? trace_bary_fwd(cfg, N, density12, sph, sph_deg, min_T, inst12, scene6, ray_to_world12, nrays, ray_o, ray_d, out_rad, out_dns,
                                                          out_hit2, out_nrm, out_cnt, visibility, dbg_ids, dbg_count, dbg_cap) : -2;
@@ -757,6 +759,7 @@ int orc_grt_trace_bwd(const GrtConfig* cfg, uint32_t N, const real* density12, c
                       const real* g_hit, real* g_density12, real* g_sph, uint32_t* dbg_ids, uint32_t* dbg_count, uint32_t dbg_cap,
                       uint8_t* round_shift) {
     orc_grt_set_primitive(cfg->primitive_type);
+    g_custom_abs = cfg->primitive_type == 5 && cfg->pipeline_type == GRUT_PIPELINE_REFERENCE_SLANG;
     const int K = cfg->max_hits_per_trace > 0 ? cfg->max_hits_per_trace : 16;
     if (K > GRT_MAX_K) return -1;
     const int ncoef = (cfg->particle_radiance_sph_degree + 1) * (cfg->particle_radiance_sph_degree + 1);

@@ -635,6 +635,92 @@ def make_grt_trace_slang_sh():
     print("wrote grt_trace_slang_sh.npz")
 
 
+# the scene of tests/test_grt_gpu.py::test_custom_primitives_with_features_use_the_slang_pipelines_unsigned_hit_distance: a few large particles
+# around the camera, so that many world boxes contain the ray origin and many points of maximum response lie BEHIND it
+GRT_INSIDE_SCENE = dict(n=400, width=32, height=24, median_scale=0.9, max_density=0.5, kind="trained")
+SLANG_SH_PRIMITIVES = (("icosahedron", "IcosaHedron"), ("octahedron", "OctraHedron"), ("tetrahedron", "TetraHedron"), ("diamond", "Diamond"),
+                       ("trihexa", "TriHexa"), ("trisurfel", "TriSurfel"), ("sphere", "Sphere"), ("custom", "Custom"))
+
+
+def make_grt_trace_slang_sh_prims():
+    """tests/golden/grt_trace_slang_sh_prims.npz: the reference's SLANG forward pipeline (referenceSlangOptix.cu) with SH radiance compiled per
+    primitive type (oracle/_ref/libref_grt_trace_slangsh_<Prim>_deg4.so) - render.pipeline_type referenceSlang with render.primitive_type != instances
+    of a model.feature_type sh run.  Scene 0 of GRT_TRACE_SCENES per primitive, laid beside the hand-written programs' goldens (grt_trace_mesh.npz,
+    grt_trace_sphere.npz).  custom additionally on GRT_INSIDE_SCENE (`custom_inside_*`), where the Slang intersection program's UNSIGNED hit distance
+    (particleDensityHitCustom, gaussianParticles.slang:489-523) admits particles the hand-written program (intersectCustomParticle) does not: that
+    program's forward outputs on the same scene are stored as `custom_inside_ref_*`."""
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from scenes import make_scene
+    px = C.CDLL(os.path.join(REF, "libref_grt_proxies.so"))
+    px.ref_enclosing_mesh.restype = C.c_uint
+    hand = {**np.load(os.path.join(HERE, "grt_trace_mesh.npz")), **np.load(os.path.join(HERE, "grt_trace_sphere.npz"))}
+    out = {}
+
+    def run(prim, fw, kw, sh_program=None):
+        sc = make_scene(**kw)
+        d12, sph = np.ascontiguousarray(sc["density12"]), np.ascontiguousarray(sc["sph"])
+        n, H, W = len(d12), kw["height"], kw["width"]
+        pos, rot, scl, dns = (np.ascontiguousarray(d12[:, 0:3]), np.ascontiguousarray(d12[:, 4:8]), np.ascontiguousarray(d12[:, 8:11]),
+                              np.ascontiguousarray(d12[:, 3]))
+        r2w = np.ascontiguousarray(np.asarray(sc["batch"]["T_to_world"][0], F)[:3, :4])
+        ro, rd = (np.ascontiguousarray(a.reshape(H, W, 3)) for a in sc["rays"])
+        feat, den, hit = np.zeros((H, W, 3), F), np.zeros((H, W, 1), F), np.zeros((H, W, 2), F)
+        cnt, vis = np.zeros((H, W, 1), F), np.zeros(n, np.int32)
+        tail = (W, H, _p(r2w), _p(ro), _p(rd))
+        tail2 = (C.c_float(MIN_T_GRT), C.c_float(MIN_RESPONSE), C.c_float(MIN_ALPHA), _p(feat), _p(den), _p(hit), _p(cnt), _p(vis))
+        if prim == "sphere":
+            ctr, rad = np.zeros((n, 3), F), np.zeros(n, F)
+            px.ref_enclosing_spheres(C.c_uint(n), _p(pos), _p(rot), _p(scl), _p(dns), C.c_float(MIN_RESPONSE), C.c_uint(1), C.c_float(4), _p(ctr), _p(rad))
+            box = np.concatenate([(ctr - rad[:, None]).min(0), (ctr + rad[:, None]).max(0)]).astype(F)
+            fw.ref_grt_trace_slang_fwd_sphere(C.c_uint(n), _p(ctr), _p(rad), _p(d12), _p(sph), *tail, _p(box), *tail2)
+        elif prim == "custom":
+            aabb, tf = np.zeros((n, 6), F), np.zeros((n, 12), F)
+            px.ref_enclosing_proxies(C.c_uint(n), _p(pos), _p(rot), _p(scl), _p(dns), C.c_float(MIN_RESPONSE), C.c_uint(1), C.c_float(4), _p(aabb), _p(tf))
+            box = np.concatenate([aabb[:, :3].min(0), aabb[:, 3:].max(0)]).astype(F)
+            if sh_program is not None:   # the hand-written forward program on the same boxes (ref_grt_trace.cpp -DREF_CUSTOM)
+                nrm = np.zeros((H, W, 3), F)
+                sh_program.ref_grt_trace_fwd_custom(C.c_uint(n), _p(aabb), _p(d12), _p(sph), *tail, _p(box), C.c_float(MIN_T_GRT), C.c_float(MIN_RESPONSE),
+                                                    C.c_float(MIN_ALPHA), C.c_uint(3), _p(feat), _p(den), _p(hit), _p(nrm), _p(cnt), _p(vis))
+            else:
+                fw.ref_grt_trace_slang_fwd_custom(C.c_uint(n), _p(aabb), _p(d12), _p(sph), *tail, _p(box), *tail2)
+        else:
+            code, _ = MESH_PRIMITIVES[prim]
+            verts, tris, nv = np.zeros((n * 12, 3), F), np.zeros((n * 20, 3), np.int32), C.c_uint(0)
+            nt = px.ref_enclosing_mesh(code, C.c_uint(n), _p(pos), _p(rot), _p(scl), _p(dns), C.c_float(MIN_RESPONSE), C.c_uint(1), C.c_float(4), _p(verts), _p(tris),
+                                       C.byref(nv))
+            verts, tris = np.ascontiguousarray(verts[:n * nv.value]), np.ascontiguousarray(tris[:n * nt])
+            box = np.concatenate([verts.min(0), verts.max(0)]).astype(F)
+            fw.ref_grt_trace_slang_fwd_mesh(C.c_uint(n), C.c_uint(nt), _p(verts), _p(tris), _p(d12), _p(sph), *tail, _p(box), *tail2)
+        return dict(features=feat, density=den, hit_distance=hit, hits_count=cnt, visibility=vis, scene_box=box)
+
+    def compare(tag, a, b):
+        rays = int((a["hits_count"] != b["hits_count"]).sum())
+        print(f"slang-sh {tag} against the hand-written program: hit counts differ on {rays} of {a['hits_count'].size} rays (totals "
+              f"{int(a['hits_count'].sum())} / {int(b['hits_count'].sum())}), max |d features| {np.abs(a['features'] - b['features']).max():.3e} "
+              f"({int((np.abs(a['features'] - b['features']).max(-1) > 1e-4).sum())} pixels above 1e-4), |d density| "
+              f"{np.abs(a['density'] - b['density']).max():.3e}, |d hit distance| {np.abs(a['hit_distance'] - b['hit_distance']).max():.3e}, "
+              f"visibility differs on {int(((a['visibility'] != 0) != (b['visibility'] != 0)).sum())} particles")
+
+    for prim, tag in SLANG_SH_PRIMITIVES:
+        fw = C.CDLL(os.path.join(REF, f"libref_grt_trace_slangsh_{tag}_deg4.so"))
+        assert fw.ref_grt_slang_ray_feature_dim() == 3
+        o = run(prim, fw, GRT_TRACE_SCENES[0])
+        for name, a in o.items():
+            out[f"{prim}_s0_{name}"] = a
+        compare(f"{prim} scene 0", o, {k: hand[f"{prim}_s0_{k}"] for k in ("features", "density", "hit_distance", "hits_count", "visibility")})
+        if prim == "custom":
+            o = run(prim, fw, GRT_INSIDE_SCENE)
+            ref = run(prim, fw, GRT_INSIDE_SCENE, sh_program=C.CDLL(os.path.join(REF, "libref_grt_trace_Custom_deg4.so")))
+            for name, a in o.items():
+                out[f"custom_inside_{name}"] = a
+            for name, a in ref.items():
+                out[f"custom_inside_ref_{name}"] = a
+            compare("custom, camera inside", o, ref)
+    np.savez_compressed(os.path.join(HERE, "grt_trace_slang_sh_prims.npz"), **out)
+    print("wrote grt_trace_slang_sh_prims.npz")
+
+
 # ---- the reference's 3DGUT kernels (projection, render, renderBackward) on the host --------------------------------------------
 GUT_RENDER_SCENES = [
     dict(n=300, width=40, height=36, median_scale=0.12, max_density=0.7),            # translucent: tens of hits per ray, ragged tiles
@@ -943,7 +1029,7 @@ def make_playground():
 if __name__ == "__main__":
     import sys
     only = [a for a in sys.argv[1:] if a.startswith("--only=")]
-    which = only[0][len("--only="):].split(",") if only else ["per_hit", "adam", "camera", "projector", "grt_proxies", "grt_trace", "grt_trace_mesh", "gut_render", "playground", "gut_nht", "grt_trace_nht", "grt_trace_nht_mesh", "grt_trace_slang_sh", "grt_trace_sphere", "grt_trace_bary", "gut_hit_seed77"]
+    which = only[0][len("--only="):].split(",") if only else ["per_hit", "adam", "camera", "projector", "grt_proxies", "grt_trace", "grt_trace_mesh", "gut_render", "playground", "gut_nht", "grt_trace_nht", "grt_trace_nht_mesh", "grt_trace_slang_sh", "grt_trace_sphere", "grt_trace_bary", "gut_hit_seed77", "grt_trace_slang_sh_prims"]
     if "--adam-only" in sys.argv:
         which = ["adam"]
     if "per_hit" in which:
@@ -979,3 +1065,5 @@ if __name__ == "__main__":
         make_grt_trace_sphere()
     if "grt_trace_bary" in which:
         make_grt_trace_bary()
+    if "grt_trace_slang_sh_prims" in which:   # (after grt_trace_mesh / grt_trace_sphere: it prints its differences against them)
+        make_grt_trace_slang_sh_prims()

@@ -1113,3 +1113,19 @@ def assert_grt_full_parity(stats):
         assert stats["G_round_shift_rays"] <= 5e-3 * stats["T_rays_compared"], stats
         for kname in list(GRAD_SLICES) + ["sph"]:   # BASELINE's bar for the DEFAULT configuration, no ray exempted but the compositing flips
             assert stats[f"G_replay_unmasked_grad_{kname}_rel_err"] < 1e-3, (kname, stats)
+
+
+def unsigned_only_pair(signed, unsigned):
+    """(ray, particle): a ray of two oracle.grt_forward(..., dbg_cap=...) runs of one scene - `signed` at pipeline_type 0, `unsigned` at 2 - that
+    processes `particle` under the unsigned custom hit distance only; of all such pairs the one whose ray processes the fewest hits (so that the
+    particle's weight on the ray is as large as it gets)."""
+    best = None
+    for r in range(unsigned["hit_ids"].shape[0]):
+        n0, n2 = int(signed["hit_num"][r]), int(unsigned["hit_num"][r])
+        if n2 > unsigned["hit_ids"].shape[1] or n0 > signed["hit_ids"].shape[1]:
+            continue
+        extra = [int(p) for p in unsigned["hit_ids"][r, :n2] if p not in set(signed["hit_ids"][r, :n0].tolist())]
+        if extra and (best is None or n2 < best[0]):
+            best = (n2, r, extra[0])
+    assert best is not None, "no ray processes a particle under the unsigned convention only"
+    return best[1], best[2]

@@ -1193,6 +1193,194 @@ def test_custom_primitives_with_features_use_the_slang_pipelines_unsigned_hit_di
     assert ora["hit_count"].sum() > sh["hit_count"].sum(), (float(ora["hit_count"].sum()), float(sh["hit_count"].sum()))
 
 
+# ---- render.pipeline_type referenceSlang with SH radiance -------------------------------------------------------------------------------------
+def _golden_dir():
+    import os
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    if os.path.join(here, "golden") not in sys.path:
+        sys.path.insert(0, os.path.join(here, "golden"))
+    return os.path.join(here, "golden")
+
+
+def _fenced_against_golden(out, g, prefix, label):
+    """The fences of test_custom_primitives_match_reference_programs_golden on a forward frame: accepted-hit counts may differ on 1 % of the rays
+    (flips), 2 % more may carry tied hits in the other order (radiance within 5e-2), opacity within 1e-4 on the rest, visibility within
+    3 x (flips + tied).  Prints what it measured."""
+    import torch
+    cnt = out["hits_count"][0].detach().cpu().numpy()
+    flips = (cnt != g[f"{prefix}_hits_count"])[..., 0]
+    e = np.abs(out["pred_features"][0].detach().cpu().numpy() - g[f"{prefix}_features"]).max(-1)
+    hd = g[f"{prefix}_hit_distance"]
+    e_d = np.abs(out["pred_dist"][0].detach().cpu().numpy() - hd[..., :1])[..., 0]
+    tied = ~flips & ((e > 1e-4) | (e_d > 1e-4 * max(1.0, np.abs(hd).max())))
+    ok = ~flips & ~tied
+    e_o = np.abs(out["pred_opacity"][0].detach().cpu().numpy() - g[f"{prefix}_density"])[..., 0]
+    vis = out["mog_visibility"].view(-1).view(torch.int32).cpu().numpy() != 0
+    dvis = int((vis != (g[f"{prefix}_visibility"] != 0)).sum())
+    print(f"{label}: {int(flips.sum())} flips, {int(tied.sum())} tied of {flips.size} rays; max |d radiance| on the rest {e[ok].max():.2e}, "
+          f"|d opacity| {e_o[ok].max():.2e}; visibility differs on {dvis} particles")
+    assert flips.mean() <= 0.01, f"{label}: {int(flips.sum())} rays with a different number of accepted hits"
+    assert tied.mean() <= 0.02 and (not tied.any() or e[tied].max() < 5e-2)
+    assert e_o[ok].max() < 1e-4
+    assert dvis <= 3 * int((flips | tied).sum())
+    return cnt
+
+
+def _forward_only(scene, **render_kw):
+    import torch
+    tr = _tracer(**render_kw)
+    g = syn.SimpleGaussians(scene["density12"], scene["sph"], requires_grad=False)
+    tr.build_acc(g, rebuild=True)
+    with torch.no_grad():
+        out = tr.render(g, torch_batch(scene["batch"], "cuda"))
+    torch.cuda.synchronize()
+    return tr, out
+
+
+@pytest.mark.parametrize("prim", ["instances", "icosahedron", "trihexa", "sphere", "custom"])
+def test_slang_pipeline_with_sh_radiance_matches_reference_slang_programs_golden(prim):
+    """render.pipeline_type = referenceSlang with SH radiance, per primitive, DIRECTLY against the reference's Slang forward program compiled for
+    that primitive over the emulated OptiX (tests/golden/grt_trace_slang_sh.npz for the instances, grt_trace_slang_sh_prims.npz for the rest),
+    scene 0 of GRT_TRACE_SCENES - outside the cloud: the Slang program equals the hand-written one there, bit for bit (test_oracle_cpu.py), and so
+    must the two pipeline names' frames."""
+    import os
+    gdir = _golden_dir()
+    import make_golden
+    if prim == "instances":
+        g, prefix = np.load(os.path.join(gdir, "grt_trace_slang_sh.npz")), "s0"
+    else:
+        g, prefix = np.load(os.path.join(gdir, "grt_trace_slang_sh_prims.npz")), f"{prim}_s0"
+    scene = make_scene(**make_golden.GRT_TRACE_SCENES[0])
+    tr, out = _forward_only(scene, pipeline_type="referenceSlang", primitive_type=prim)
+    assert tr.tracer_wrapper.cfg.pipeline_type == 2
+    cnt = _fenced_against_golden(out, g, prefix, f"referenceSlang + {prim}, scene 0")
+    _, ref = _forward_only(scene, primitive_type=prim)
+    assert np.array_equal(cnt, ref["hits_count"][0].cpu().numpy())   # outside the cloud the `reference` frame counts the same hits
+    assert cnt.max() >= 15
+
+
+def _custom_inside():
+    """The camera-inside scene of tests/golden/make_golden.py (GRT_INSIDE_SCENE) and its goldens: `custom_inside_*` = the reference's Slang forward
+    program (unsigned custom hit distance), `custom_inside_ref_*` = the hand-written one (signed)."""
+    import os
+    gdir = _golden_dir()
+    import make_golden
+    scene = make_scene(**make_golden.GRT_INSIDE_SCENE)
+    scene["T"] = scene["batch"]["T_to_world"][0]
+    return scene, np.load(os.path.join(gdir, "grt_trace_slang_sh_prims.npz"))
+
+
+_SLANG_CUSTOM = dict(pipeline_type="referenceSlang", primitive_type="custom")
+_inside_cache = {}
+
+
+def _custom_inside_checker():
+    """One GPU debug frame of the camera-inside scene under referenceSlang + custom + SH and the checker's frames on the GPU-built records, at
+    pipeline_type 2 (unsigned distance) and 0 (signed): computed once, shared by the tests below, not modified by them."""
+    if not _inside_cache:
+        scene, _ = _custom_inside()
+        n = len(scene["density12"])
+        tr, res, inst, scene_aabb = _gpu_hits(scene, **_SLANG_CUSTOM)
+        box8 = tr.tracer_wrapper.custom_boxes(n, "cuda").cpu().numpy()
+        ora = {p: oracle.grt_forward(oracle.default_grt_config(primitive_type=5, pipeline_type=p), scene["density12"], scene["sph"], 3, 1e-3, scene["T"],
+                                     *scene["rays"], inst=inst, scene=scene_aabb, dbg_cap=256, box8=box8) for p in (0, 2)}
+        _inside_cache.update(scene=scene, gpu=res, ora=ora)
+    return _inside_cache["scene"], _inside_cache["gpu"], _inside_cache["ora"]
+
+
+def test_custom_primitives_under_the_slang_pipeline_follow_the_slang_hit_test():
+    """render.pipeline_type = referenceSlang + primitive_type custom + SH radiance with the camera INSIDE large particles: the Slang intersection
+    program (particleDensityHitCustom, gaussianParticles.slang:489-523) reports an unsigned hit distance, so particles whose point of maximum
+    response lies behind the ray origin are candidates - the frame must be the Slang program's (`custom_inside_*`, same fences as every golden
+    comparison), and NOT the `reference` pipeline's frame of the same scene, which follows the hand-written program's signed distance
+    (`custom_inside_ref_*`): the two HIP frames differ in the accepted-hit count on at least a quarter of the rays (the programs: 555 of 768)."""
+    scene, g = _custom_inside()
+    tr, out = _forward_only(scene, **_SLANG_CUSTOM)
+    cnt = _fenced_against_golden(out, g, "custom_inside", "referenceSlang + custom, camera inside")
+    _, ref = _forward_only(scene, primitive_type="custom")
+    cnt_ref = _fenced_against_golden(ref, g, "custom_inside_ref", "reference + custom, camera inside")
+    differ = (cnt != cnt_ref)[..., 0]
+    print(f"referenceSlang vs reference frame: hit counts differ on {int(differ.sum())} of {differ.size} rays")
+    assert differ.mean() >= 0.25
+    assert cnt.sum() > cnt_ref.sum()
+
+
+def test_custom_primitives_under_the_slang_pipeline_hit_order_equals_oracle():
+    """The camera-inside analogue of test_custom_primitives_hit_order_equals_oracle: every ray's SEQUENCE of processed particles under
+    referenceSlang + custom + SH equals the checker's at pipeline_type 2 (unsigned distance) given the GPU-built records - and is not the
+    checker's at pipeline_type 0."""
+    scene, (feat, dns, hit, nrm, cnt, vis, ids, num), ora = _custom_inside_checker()
+    o2 = ora[2]
+    num = num.astype(np.int64)
+    assert np.array_equal(num, o2["hit_num"].astype(np.int64)), f"{(num != o2['hit_num']).sum()} rays with a different number of processed hits"
+    k = np.minimum(num, 256)
+    got, ref = ids.view(np.uint32), o2["hit_ids"]
+    for r in range(scene["H"] * scene["W"]):
+        assert np.array_equal(got[r, :k[r]], ref[r, :k[r]]), f"ray {r}: order differs"
+    assert num.max() > 20
+    assert np.abs(feat[0] - o2["features"]).max() < 1e-4 and np.abs(dns[0] - o2["density"]).max() < 1e-4 and np.array_equal(cnt[0], o2["hit_count"])
+    assert np.array_equal(vis.view(np.int32).reshape(-1) != 0, o2["visibility"] != 0)
+    assert (num != ora[0]["hit_num"].astype(np.int64)).mean() >= 0.25
+
+
+@pytest.mark.parametrize("replay", [True, False])
+def test_custom_primitives_under_the_slang_pipeline_gradients_match_oracle(replay):
+    """The default (replayed) backward and the traversal fallback (render.backward_hit_replay false) under referenceSlang + custom + SH on the
+    camera-inside scene against oracle.grt_backward at pipeline_type 2, random upstream gradients.  The backward is pinned through the checker
+    only: the reference's referenceSlangBwdOptix.cu is not built on the host (its per-hit backward functions are Slang autodiff output with no
+    restatement in the stand-in); the checker's forward convention is pinned by the Slang program's golden (test_oracle_cpu.py).
+    Which particles tell the conventions apart: on this scene the unsigned distance adds hits in FRONT, so no particle becomes visible through it
+    (visible at pipeline_type 2 and invisible at 0: none; three the other way round) - the selection by visibility has nothing to select.  Instead:
+    the particles visible at 0 only must get NO gradient, and an upstream gradient on ONE ray that processes a particle under the unsigned
+    convention only (parity_util.unsigned_only_pair) must give that particle the checker's nonzero gradient."""
+    from parity_util import unsigned_only_pair
+    scene, _, ora = _custom_inside_checker()
+    H, W = scene["H"], scene["W"]
+    rng = np.random.default_rng(4)
+    g_rad = rng.normal(size=(H, W, 3)).astype(np.float32)
+    g_dns = rng.normal(size=(H, W, 1)).astype(np.float32)
+    cfg = oracle.default_grt_config(primitive_type=5, pipeline_type=2)
+    kw = dict(_SLANG_CUSTOM, backward_hit_replay=replay)
+    gd, gs = _render(scene, g_rad, g_dns, None, **kw)["grads"]
+    rd, rs = oracle.grt_backward(cfg, 3, 1e-3, ora[2], g_rad, g_dns, np.zeros_like(g_dns))
+    print(f"replay={replay}: rel err geometry {rel_err(gd[:, :11], rd[:, :11]):.2e}, SH {rel_err(gs, rs):.2e}")
+    assert rel_err(gd[:, :11], rd[:, :11]) < 1e-3 and rel_err(gs, rs) < 1e-3
+    gone = (ora[0]["visibility"] != 0) & (ora[2]["visibility"] == 0)
+    assert gone.sum() >= 1 and not ((ora[2]["visibility"] != 0) & (ora[0]["visibility"] == 0)).any()
+    assert np.abs(gd[gone]).max() == 0 and np.abs(gs[gone]).max() == 0
+    rd0, _ = oracle.grt_backward(oracle.default_grt_config(primitive_type=5), 3, 1e-3, ora[0], g_rad, g_dns, np.zeros_like(g_dns))
+    assert np.abs(rd0[gone, :11]).max() > 0 and rel_err(rd0[:, :11], rd[:, :11]) > 1e-3   # (the signed convention's gradient is another one)
+    # one ray, one particle that only the unsigned convention reaches on it
+    ray, pid = unsigned_only_pair(ora[0], ora[2])
+    m_rad, m_dns = np.zeros_like(g_rad), np.zeros_like(g_dns)
+    m_rad.reshape(-1, 3)[ray], m_dns.reshape(-1, 1)[ray] = g_rad.reshape(-1, 3)[ray], g_dns.reshape(-1, 1)[ray]
+    gd1, gs1 = _render(scene, m_rad, m_dns, None, **kw)["grads"]
+    rd1, rs1 = oracle.grt_backward(cfg, 3, 1e-3, ora[2], m_rad, m_dns, np.zeros_like(g_dns))
+    assert np.abs(rd1[pid, :11]).max() > 0 and np.abs(gd1[pid, :11]).max() > 0
+    assert rel_err(gd1[:, :11], rd1[:, :11]) < 1e-3 and rel_err(gs1, rs1) < 1e-3
+    assert np.abs(gd1[pid, :11] - rd1[pid, :11]).max() <= 1e-3 * np.abs(rd1[pid, :11]).max()
+
+
+def test_custom_primitives_under_the_slang_pipeline_packet_lists_equal_the_tree_walk(monkeypatch):
+    """Packet lists and tree walk under referenceSlang + custom + SH with the camera inside the particles' world boxes: the lists' keys and
+    bounds must hold for the UNSIGNED distance (a particle whose maximum lies behind the origin sorts by |t*|, within the 3-sigma sphere of its
+    centre's distance: tests/test_grt_custom_slack_cpu.py) - every output and every ray's sequence bit-equal.  The lists ARE used here (one ray
+    origin; world boxes that contain it get key 0)."""
+    scene, _ = _custom_inside()
+    (a, n_lists), (b, n_walk) = _hits_with(scene, monkeypatch, False, **_SLANG_CUSTOM), _hits_with(scene, monkeypatch, True, **_SLANG_CUSTOM)
+    assert n_lists > 0 and n_walk == 0
+    num = a[7].reshape(-1).astype(np.int64)
+    for x, y, name in zip(a, b, ("features", "density", "hit_distance", "normals", "hit_count", "visibility", "ids", "num")):
+        if name == "ids":
+            for r in range(num.size):
+                k = min(int(num[r]), 128)
+                assert np.array_equal(x.reshape(num.size, -1)[r, :k], y.reshape(num.size, -1)[r, :k]), f"ray {r}: order differs"
+        else:
+            assert np.array_equal(x, y), name
+    assert num.max() > 20
+
+
 def test_nht_forward_matches_reference_slang_programs_golden():
     """The HIP 3DGRT path with neural harmonic features DIRECTLY against tests/golden/grt_trace_nht.npz — the reference's Slang forward
     pipeline (referenceSlangOptix.cu) run on the host over the emulated traversal: accepted-hit counts, visibility, 24 ray features."""

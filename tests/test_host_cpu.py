@@ -202,6 +202,37 @@ def test_grt_configuration_defaults_and_unsupported_pipelines():
             grt.grt_config_from_conf({"render": bad})
 
 
+def test_grt_config_carries_the_slang_flavour_and_refuses_mixed_flavours_for_custom_primitives():
+    """render.pipeline_type referenceSlang -> GrtConfig.pipeline_type 2 (GRUT_PIPELINE_REFERENCE_SLANG), with SH radiance and with features: the
+    kernels switch the custom primitives' hit distance on it.  A forward of one flavour with the backward of the other would differentiate
+    another candidate set than the forward traced when primitive_type is custom: refused there, accepted for every other primitive (the two
+    flavours' candidate tests are the same)."""
+    grt = importlib.import_module("3dgrut_amd.grt_tracer")
+    nht = {"feature_type": "nht", "nht_features": {"dim": 48, "activation": {"type": "sincos", "num_frequencies": 1}, "interpolation_type": "barycentric"}}
+    assert grt.grt_config_from_conf({"render": {"pipeline_type": "referenceSlang"}}).pipeline_type == 2
+    assert grt.grt_config_from_conf({"render": {"pipeline_type": "referenceSlang"}, "model": nht}).pipeline_type == 2
+    assert grt.grt_config_from_conf({"render": {"pipeline_type": "reference"}}).pipeline_type == 0
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "grut_amd.h")).read()
+    assert "GRUT_PIPELINE_REFERENCE_SLANG = 2" in header
+    mixed = ({"pipeline_type": "reference", "backward_pipeline_type": "referenceSlangBwd"},
+             {"pipeline_type": "referenceSlang", "backward_pipeline_type": "referenceBwd"})
+    for prim in ("instances", "icosahedron", "octahedron", "tetrahedron", "diamond", "custom", "trihexa", "sphere"):
+        for k, m in enumerate(mixed):
+            if prim == "custom":
+                with pytest.raises(NotImplementedError, match="custom"):
+                    grt.grt_config_from_conf({"render": dict(m, primitive_type=prim)})
+            else:
+                assert grt.grt_config_from_conf({"render": dict(m, primitive_type=prim)}).pipeline_type == (0, 2)[k]
+        same = grt.grt_config_from_conf({"render": {"pipeline_type": "referenceSlang", "backward_pipeline_type": "referenceSlangBwd", "primitive_type": prim}})
+        assert (same.pipeline_type, same.primitive_type) == (2, grt._abi.GRT_PRIMITIVES[prim])
+    # trisurfel: the Slang forward program with SH radiance is NOT the hand-written one (test_oracle_cpu.py:
+    # test_slang_sh_program_for_trisurfel_is_not_the_hand_written_program) - refused with the measured difference, `reference` still served
+    with pytest.raises(NotImplementedError, match="315 of 384 rays"):
+        grt.grt_config_from_conf({"render": {"pipeline_type": "referenceSlang", "primitive_type": "trisurfel"}})
+    with pytest.raises(NotImplementedError, match="315 of 384 rays"):
+        grt.grt_config_from_conf({"render": {"pipeline_type": "referenceSlang", "backward_pipeline_type": "referenceBwd", "primitive_type": "trisurfel"}})
+    assert grt.grt_config_from_conf({"render": {"pipeline_type": "reference", "primitive_type": "trisurfel"}}).pipeline_type == 0
+
 def test_bench_launches_itself_for_multi_gpu_runs():
     """`python bench.py --gpus N` from a bare shell must start its own ranks (torch.distributed.run); without enough devices for RCCL it
     says so instead of dying in a launcher it never started."""

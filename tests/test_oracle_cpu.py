@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import oracle
+from parity_util import unsigned_only_pair
 from scenes import make_scene, rel_err
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -1152,6 +1153,123 @@ def test_slang_forward_with_sh_radiance_is_the_reference_forward():
         assert np.abs(a[f"s{k}_hit_distance"] - b[f"s{k}_hit_distance"]).max() <= 1e-6
         k += 1
     assert k == 2
+
+
+_SLANG_SH_EQUAL_PRIMS = ["icosahedron", "octahedron", "tetrahedron", "diamond", "trihexa", "sphere", "custom"]
+
+
+def _hand_written_golden(prim):
+    return np.load(os.path.join(HERE, "golden", "grt_trace_sphere.npz" if prim == "sphere" else "grt_trace_mesh.npz"))
+
+
+@pytest.mark.parametrize("prim", _SLANG_SH_EQUAL_PRIMS)
+def test_slang_sh_program_per_primitive_is_the_hand_written_program(prim):
+    """render.pipeline_type = referenceSlang with SH radiance and render.primitive_type != instances runs on the kernels of the `reference`
+    pipeline.  Pinned program against program, in the terms of test_slang_forward_with_sh_radiance_is_the_reference_forward:
+    referenceSlangOptix.cu compiled for the primitive (tests/golden/grt_trace_slang_sh_prims.npz) against referenceOptix.cu compiled for it
+    (grt_trace_mesh.npz / grt_trace_sphere.npz), scene 0 - outside the cloud, where the custom primitives' signed and unsigned hit distances
+    coincide too (measured: equal; the camera-inside scene is the one that tells them apart, below)."""
+    a = np.load(os.path.join(HERE, "golden", "grt_trace_slang_sh_prims.npz"))
+    b = _hand_written_golden(prim)
+    for key in ("features", "density", "hits_count", "visibility"):
+        assert np.array_equal(a[f"{prim}_s0_{key}"], b[f"{prim}_s0_{key}"]), key
+    assert np.abs(a[f"{prim}_s0_hit_distance"] - b[f"{prim}_s0_hit_distance"]).max() <= 1e-6
+    assert a[f"{prim}_s0_hits_count"].max() >= 15 and np.abs(a[f"{prim}_s0_features"]).max() > 0.5
+
+
+def test_slang_sh_program_for_trisurfel_is_not_the_hand_written_program():
+    """trisurfel is the exception: the Slang forward program as the host stand-in builds it (oracle/ref/shim/3dgrt_slang has no surfel mode:
+    GAUSSIAN_PARTICLE_SURFEL, gaussianParticles.slang:49-51, 125-127) and the hand-written program with its surfel branches disagree - measured
+    by the golden generator: accepted-hit counts on 315 of 384 rays (6019 / 6419 hits), 0.52 in radiance, 0.48 in opacity, 2.1 in hit distance, 33
+    visibility flags.  grt_config_from_conf therefore refuses referenceSlang + trisurfel + SH (test_host_cpu.py) instead of serving it with the
+    `reference` kernels; the figures in its message are these."""
+    a = np.load(os.path.join(HERE, "golden", "grt_trace_slang_sh_prims.npz"))
+    b = _hand_written_golden("trisurfel")
+    ca, cb = a["trisurfel_s0_hits_count"], b["trisurfel_s0_hits_count"]
+    assert (int((ca != cb).sum()), ca.size, int(ca.sum()), int(cb.sum())) == (315, 384, 6019, 6419)
+    assert abs(float(np.abs(a["trisurfel_s0_features"] - b["trisurfel_s0_features"]).max()) - 0.52) < 0.005
+    assert abs(float(np.abs(a["trisurfel_s0_density"] - b["trisurfel_s0_density"]).max()) - 0.48) < 0.005
+    assert int(((a["trisurfel_s0_visibility"] != 0) != (b["trisurfel_s0_visibility"] != 0)).sum()) == 33
+
+
+def _custom_inside_scene():
+    sys.path.insert(0, os.path.join(HERE, "golden"))
+    import make_golden
+    sc = make_scene(**make_golden.GRT_INSIDE_SCENE)
+    return sc, sc["batch"]["T_to_world"][0]
+
+
+def test_custom_inside_scene_separates_the_slang_program_from_the_hand_written_one():
+    """The power of the camera-inside scene (tests/golden/make_golden.py: GRT_INSIDE_SCENE): with primitive_type custom the Slang intersection
+    program reports an UNSIGNED hit distance (particleDensityHitCustom, gaussianParticles.slang:489-523), the hand-written one a signed one
+    (intersectCustomParticle, gaussianParticles.cuh:407-441), so particles whose point of maximum response lies behind the ray origin are
+    candidates of the first only.  `custom_inside_*` (Slang program) against `custom_inside_ref_*` (hand-written program): measured 555 of 768
+    rays with another accepted-hit count (17 875 / 17 163 hits), 0.183 in radiance, 3 visibility flags.  If the scene is ever changed so that
+    the two programs agree on it, the GPU tests that use it would pass without telling the two conventions apart: this test fails first."""
+    g = np.load(os.path.join(HERE, "golden", "grt_trace_slang_sh_prims.npz"))
+    differ = (g["custom_inside_hits_count"] != g["custom_inside_ref_hits_count"])[..., 0]
+    d_rad = np.abs(g["custom_inside_features"] - g["custom_inside_ref_features"]).max(-1)
+    print(f"custom_inside: hit counts differ on {int(differ.sum())} of {differ.size} rays, max radiance difference {d_rad.max():.3f}")
+    assert differ.mean() >= 0.25
+    assert d_rad.max() > 1e-2
+    assert g["custom_inside_hits_count"].sum() > g["custom_inside_ref_hits_count"].sum()
+
+
+def test_grt_checker_follows_the_slang_custom_hit_test_under_pipeline_type_2():
+    """orc_grt_trace_fwd with cfg.pipeline_type = GRUT_PIPELINE_REFERENCE_SLANG takes the unsigned custom distance: against the Slang program's
+    golden on the camera-inside scene at most 1 % of the rays may carry another accepted-hit count (expected: none), radiance and opacity
+    within 1e-4 on the rest.  With pipeline_type 0 (signed distance) the same checker must MISS that golden on at least a quarter of the rays -
+    and reproduce the hand-written program's instead."""
+    g = np.load(os.path.join(HERE, "golden", "grt_trace_slang_sh_prims.npz"))
+    sc, T = _custom_inside_scene()
+    slang = oracle.grt_forward(oracle.default_grt_config(primitive_type=5, pipeline_type=2), sc["density12"], sc["sph"], 3, 1e-3, T, *sc["rays"])
+    flips = (slang["hit_count"] != g["custom_inside_hits_count"])[..., 0]
+    print(f"checker pipeline_type 2 vs Slang golden: {int(flips.sum())} of {flips.size} rays with another hit count, "
+          f"total {int(slang['hit_count'].sum())} / {int(g['custom_inside_hits_count'].sum())}")
+    assert flips.mean() <= 0.01
+    ok = ~flips
+    assert np.abs(slang["features"] - g["custom_inside_features"])[ok].max() <= 1e-4
+    assert np.abs(slang["density"] - g["custom_inside_density"])[ok].max() <= 1e-4
+    assert ((slang["visibility"] != 0) != (g["custom_inside_visibility"] != 0)).sum() <= 3 * int(flips.sum())
+    hand = oracle.grt_forward(oracle.default_grt_config(primitive_type=5, pipeline_type=0), sc["density12"], sc["sph"], 3, 1e-3, T, *sc["rays"])
+    miss = (hand["hit_count"] != g["custom_inside_hits_count"])[..., 0]
+    print(f"checker pipeline_type 0 vs Slang golden: {int(miss.sum())} of {miss.size} rays with another hit count")
+    assert miss.mean() >= 0.25
+    assert ((hand["hit_count"] != g["custom_inside_ref_hits_count"])[..., 0]).mean() <= 0.01
+    # the flavour is per call: the feature entry points keep the unsigned distance, a later pipeline_type 0 call is signed again
+    again = oracle.grt_forward(oracle.default_grt_config(primitive_type=5, pipeline_type=2), sc["density12"], sc["sph"], 3, 1e-3, T, *sc["rays"])
+    assert np.array_equal(again["hit_count"], slang["hit_count"])
+
+
+def test_grt_checker_backward_follows_the_forward_convention_for_custom_primitives():
+    """orc_grt_trace_bwd at pipeline_type 2 differentiates the hits the unsigned test admits, and only those.  On the camera-inside scene the
+    unsigned convention adds hits in FRONT (17 875 against 17 163 accepted), which use up transmittance: no particle becomes visible through it,
+    three (67, 233, 284) stop being reached at all - visible sets 80 of 83.  So: of those three one gets a gradient at pipeline_type 0, none does
+    at 2; and on a single ray that processes a particle under the unsigned convention only (unsigned_only_pair), an upstream gradient on that ray
+    alone gives that particle a gradient at 2 and none at 0.  (The reference's referenceSlangBwdOptix.cu is not built on the host - its per-hit
+    backward functions are Slang autodiff output with no restatement in the stand-in - so the Slang backward is pinned through this checker: the
+    forward convention against the program's golden above, the per-hit backward shared with the `reference` path, which the hand-written
+    backward program's goldens pin.)"""
+    sc, T = _custom_inside_scene()
+    H, W = sc["H"], sc["W"]
+    rng = np.random.default_rng(4)
+    g_rad, g_dns = rng.normal(size=(H, W, 3)).astype(np.float32), rng.normal(size=(H, W, 1)).astype(np.float32)
+    zero = np.zeros((H, W, 1), np.float32)
+    fwd, grad = {}, {}
+    for p in (0, 2):
+        cfg = oracle.default_grt_config(primitive_type=5, pipeline_type=p)
+        fwd[p] = oracle.grt_forward(cfg, sc["density12"], sc["sph"], 3, 1e-3, T, *sc["rays"], dbg_cap=256)
+        grad[p] = oracle.grt_backward(cfg, 3, 1e-3, fwd[p], g_rad, g_dns, zero)
+    gone = (fwd[0]["visibility"] != 0) & (fwd[2]["visibility"] == 0)
+    assert gone.sum() == 3 and not ((fwd[2]["visibility"] != 0) & (fwd[0]["visibility"] == 0)).any()
+    # (two of the three are only ever a ray's LAST hit, which the backward program's end-of-ray clip leaves out: no gradient at 0 either)
+    assert np.abs(grad[0][0][gone, :11]).max() > 0 and np.abs(grad[2][0][gone]).max() == 0 and np.abs(grad[2][1][gone]).max() == 0
+    assert rel_err(grad[2][0][:, :11], grad[0][0][:, :11]) > 1e-3
+    ray, pid = unsigned_only_pair(fwd[0], fwd[2])
+    m_rad, m_dns = np.zeros_like(g_rad), np.zeros_like(g_dns)
+    m_rad.reshape(-1, 3)[ray], m_dns.reshape(-1, 1)[ray] = g_rad.reshape(-1, 3)[ray], g_dns.reshape(-1, 1)[ray]
+    one = {p: oracle.grt_backward(oracle.default_grt_config(primitive_type=5, pipeline_type=p), 3, 1e-3, fwd[p], m_rad, m_dns, zero) for p in (0, 2)}
+    assert np.abs(one[2][0][pid, :11]).max() > 0 and np.abs(one[0][0][pid]).max() == 0
 
 
 def test_grt_backward_is_linear_in_the_upstream_gradient_and_separable_by_ray():
