@@ -159,6 +159,11 @@ class GrutDecodeConfig(C.Structure):
     _fields_ = [("mlp", GrutMlpConfig), ("sh_scale", C.c_float), ("unpremultiply_alpha", C.c_int32), ("center_ray", C.c_int32)]
 
 
+class GrutDenoiseConfig(C.Structure):
+    """include/grut_amd.h: GrutDenoiseConfig (grut_denoise, the playground's frame denoiser)."""
+    _fields_ = [("patch_radius", C.c_int32), ("search_radius", C.c_int32), ("h", C.c_float)]
+
+
 class McmcTensor(C.Structure):   # GrutMcmcTensor
     _fields_ = [("data", C.c_void_p), ("row_elems", C.c_uint32), ("role", C.c_uint32)]
 
@@ -177,6 +182,7 @@ EXPORTED_SYMBOLS = [
     "grt_debug_forward_hits", "grt_debug_fetch_instances", "grt_debug_fetch_custom_boxes", "grt_debug_fetch_lists", "grt_debug_backward_signature", "grt_build_mesh_bvh", "grt_trace_hybrid",
     "grut_selective_adam_update", "grut_pack_particles", "grut_unpack_particle_grads", "grut_activate_pack", "grut_activate_pack_backward",
     "grut_reg_partials", "grut_reg_forward", "grut_reg_backward",
+    "grut_denoise",
     "grut_mcmc_relocation", "grut_mcmc_perturb",
     "grut_mcmc_classify", "grut_mcmc_classify_scratch_bytes", "grut_mcmc_sample_plan", "grut_mcmc_relocate_rows", "grut_mcmc_append_rows",
     "grut_densify_accumulate", "grut_relayout_scan", "grut_relayout_scratch_bytes", "grut_relayout_rows", "grut_split_tail",
@@ -313,6 +319,8 @@ def _declare(lib):
     lib.grut_reg_forward.restype = C.c_int
     lib.grut_reg_backward.argtypes = [vp, C.c_uint32, fp, fp, fp, fp, fp]
     lib.grut_reg_backward.restype = C.c_int
+    lib.grut_denoise.argtypes = [vp, C.POINTER(GrutDenoiseConfig), C.c_uint32, C.c_uint32, C.c_uint32, fp, fp]
+    lib.grut_denoise.restype = C.c_int
     lib.grut_mcmc_relocation.argtypes = [vp, C.c_uint32, fp, fp, ip, fp, C.c_int, fp, fp]
     lib.grut_mcmc_relocation.restype = C.c_int
     lib.grut_mcmc_perturb.argtypes = [vp, C.c_uint32, fp, fp, fp, fp, fp, C.c_float, C.c_float, C.c_int]

@@ -1,12 +1,17 @@
-"""Hybrid mesh + Gaussian tracer: drop-in for the render path of `threedgrut_playground.tracer.Tracer`
-(threedgrut_playground/tracer.py:47-268) — `build_gs_acc`, `build_mesh_acc`, `render`, `render_playground` — over the C-ABI's
-grt_build_mesh_bvh / grt_trace_hybrid (include/grut_amd.h).  BASELINE config 5: primary rays + reflection / refraction / PBR scattering
+"""Hybrid mesh + Gaussian tracer: drop-in for `threedgrut_playground.tracer.Tracer`
+(threedgrut_playground/tracer.py:47-271) — `build_gs_acc`, `build_mesh_acc`, `render`, `render_playground`, `denoise` — over the C-ABI's
+grt_build_mesh_bvh / grt_trace_hybrid / grut_denoise (include/grut_amd.h).  BASELINE config 5: primary rays + reflection / refraction / PBR scattering
 through triangle meshes with Gaussian segments in between, forward only like the reference.
 
 Materials are the reference's `Material` objects (threedgrut_playground/utils/mesh_io.py; attribute names as tracer.py:133-170 reads
 them: diffuse_map, emissive_map, metallic_roughness_map, normal_map, diffuse_factor, emissive_factor, metallic_factor,
-roughness_factor, alpha_mode, alpha_cutoff, transmission_factor, ior) or plain dicts with those keys.  Not provided: the OptiX
-denoiser (`denoise`)."""
+roughness_factor, alpha_mode, alpha_cutoff, transmission_factor, ior) or plain dicts with those keys.
+
+`denoise` has the reference's signature and place in the engine (engine.py:1091-1094 calls it on the tonemapped frame at the end of
+every render pass, use_optix_denoiser being on by default).  THIS PROJECT'S CHOICE: the reference runs OptiX's learned LDR denoiser
+on RGB alone (hybridTracer.cpp:428-498), whose weights are not public; here the frame goes through non-local means (3dgrut_amd/denoise.py,
+csrc/denoise.hip), an exact formula on the same input.  No equivalence with the learned model is claimed.  Keys of this plugin, all
+optional: render.denoiser.patch_radius (3), render.denoiser.search_radius (7), render.denoiser.strength (the h of the model, 0.1)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,8 +19,9 @@ import ctypes as C
 import torch
 
 from . import _abi
+from . import denoise as _denoise
 from .grt_tracer import Tracer as _GrtTracer, features_for_kernel
-from .gut_tracer import _ptr, _stream_ptr
+from .gut_tracer import _conf_get, _ptr, _stream_ptr
 
 
 def _mat_get(m, key, default=None):
@@ -62,7 +68,25 @@ def native_materials(materials, device, keep):
     return arr, n
 
 
+def denoiser_parameters(conf):
+    """conf.render.denoiser.{patch_radius, search_radius, strength} -> (f, r, h); an absent key (or node) gives denoise.DEFAULTS.  Values
+    outside the model's ranges raise ValueError here, when the tracer is built, not on the first frame."""
+    node = _conf_get(_conf_get(conf, "render"), "denoiser")
+    d = _denoise.DEFAULTS
+    return _denoise.check_parameters(_conf_get(node, "patch_radius", d["patch_radius"]), _conf_get(node, "search_radius", d["search_radius"]),
+                                     _conf_get(node, "strength", d["h"]))
+
+
 class Tracer(_GrtTracer):
+    def __init__(self, conf):
+        super().__init__(conf)
+        self._denoiser = denoiser_parameters(conf)
+
+    def denoise(self, ray_radiance):
+        """threedgrut_playground/tracer.py:269-271: the frame [B, H, W, 3] (or [H, W, 3]) -> a NEW tensor of the same shape, dtype and
+        device; the argument is left as it is (the engine keeps it as rb["rgb_buffer"])."""
+        return _denoise.denoise(ray_radiance, *self._denoiser)
+
     def build_gs_acc(self, gaussians, rebuild=True):
         return self.build_acc(gaussians, rebuild)
 

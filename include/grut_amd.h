@@ -505,6 +505,34 @@ int grt_trace_hybrid(GrtHandle* handle, void* stream, const GrtFrame* frame, con
                      const float* ray_origin, const float* ray_direction, const float* ray_max_t, const GrtMesh* mesh,
                      const GrtHybridOptions* options, float* out_radiance, float* out_opacity, float* out_last_ray, uint32_t* out_bounces);
 
+/* ---- frame denoiser of the playground (replaces HybridOptixTracer::denoise, playground/hybridTracer.h:143) -------------------------
+ * The reference hands the engine's tonemapped RGB frame, and nothing else (no albedo, normal or flow layer), to OptiX's learned LDR
+ * denoiser (hybridTracer.cpp:428-498); those weights are not public.  THIS PROJECT'S CHOICE of algorithm is non-local means
+ * (Buades, Coll, Morel 2005), an exact formula on RGB alone; the call surface is the reference's.
+ * rgb_in, rgb_out: [batch, height, width, 3] f32, DEVICE, dense.  With f = patch_radius, r = search_radius, n = 3 (2f+1)^2 and
+ * X_MAX = 80, for a pixel p of image b and every OTHER pixel q of the same image with |q - p|_inf <= r that lies inside the image:
+ *   d2(p,q) = sum over o in [-f,f]^2, c in {r,g,b} of (I[clamp(p+o)]_c - I[clamp(q+o)]_c)^2     (clamp: each coordinate to the image)
+ *   x(p,q)  = min(d2(p,q) / (n h^2), X_MAX)
+ *   w(p,q)  = exp(-x(p,q))                  (>= e^-80, a normal fp32 number: no weight is ever zero)
+ *   w(p,p)  = max over those q of w(p,q), or 1 when there is no such q (a 1x1 image)
+ *   out[p]  = (sum_q w(p,q) I[q] + w(p,p) I[p]) / (sum_q w(p,q) + w(p,p))
+ * The min is a continuous clamp, not a cut to zero: with the max rule for the centre a cut would make an isolated pixel's result jump
+ * when one far neighbour crosses the threshold.  Nothing clamps the values: the frame is nominally in [0, 1].
+ * Out of place: rgb_out is written completely and rgb_in is never written (the engine keeps the input as its accumulation buffer).
+ * No address depends on a pixel's value: a NaN or inf pixel makes the outputs within r + f of it unspecified and moves no load or
+ * store.  No atomics; the order of every sum depends on (height, width, f, r) only, so two calls on one input are bitwise equal; the
+ * images of a batch never see each other.  One launch on `stream`; no scratch, no allocation, no synchronisation.
+ * GRUT_ERR_BAD_INPUT before any HIP call, with the argument named by grut_last_error: a NULL among cfg, rgb_in, rgb_out; f outside
+ * 0..4; r outside 1..16; h not finite or <= 0; height or width 0; batch * height * width >= 2^31; ranges of rgb_in and rgb_out that
+ * overlap.  batch == 0 is GRUT_OK without a launch. */
+typedef struct GrutDenoiseConfig {
+    int32_t patch_radius;             /* f: patches are (2f+1)^2 pixels; the plugin's default is 3 */
+    int32_t search_radius;            /* r: candidates are the (2r+1)^2 - 1 pixels around p; default 7 */
+    float   h;                        /* strength: the per-element patch distance at which a weight is 1/e; default 0.1 */
+} GrutDenoiseConfig;
+int grut_denoise(void* stream, const GrutDenoiseConfig* cfg, uint32_t batch, uint32_t height, uint32_t width, const float* rgb_in,
+                 float* rgb_out);
+
 int  grt_create(const GrtConfig* config, GrtHandle** handle);
 int  grt_trim(GrtHandle* handle);
 void grt_destroy(GrtHandle* handle);
