@@ -109,6 +109,15 @@ class GrutAdamGroup(C.Structure):
     ]
 
 
+class GrutDenseAdamGroup(C.Structure):
+    """include/grut_amd.h: GrutDenseAdamGroup (one tensor of grut_adam_update, torch's fused Adam state)."""
+    _fields_ = [
+        ("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("step", C.c_void_p),
+        ("numel", C.c_uint64), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+        ("weight_decay", C.c_double),
+    ]
+
+
 VIS_NONE, VIS_BOOL_U8, VIS_INT32, VIS_FLOAT_BITS = range(4)
 # GrtConfig::primitive_type (render.primitive_type, optixTracer.cpp:176-201)
 GRT_PRIMITIVES = {"instances": 0, "icosahedron": 1, "octahedron": 2, "tetrahedron": 3, "diamond": 4, "custom": 5, "trisurfel": 6, "trihexa": 7, "sphere": 8}
@@ -180,7 +189,7 @@ EXPORTED_SYMBOLS = [
     "grut_scan_scratch_bytes", "grut_debug_sort_pairs_u32", "grut_debug_scan_gather_u32", "gut_debug_tile_ranges", "grt_debug_list_ranges",
     "grt_create", "grt_destroy", "grt_build_bvh", "grt_forward", "grt_backward", "grt_timings", "grt_stats", "grt_debug_fetch_work",
     "grt_debug_forward_hits", "grt_debug_fetch_instances", "grt_debug_fetch_custom_boxes", "grt_debug_fetch_lists", "grt_debug_backward_signature", "grt_build_mesh_bvh", "grt_trace_hybrid",
-    "grut_selective_adam_update", "grut_pack_particles", "grut_unpack_particle_grads", "grut_activate_pack", "grut_activate_pack_backward",
+    "grut_selective_adam_update", "grut_adam_update", "grut_pack_particles", "grut_unpack_particle_grads", "grut_activate_pack", "grut_activate_pack_backward",
     "grut_reg_partials", "grut_reg_forward", "grut_reg_backward",
     "grut_denoise",
     "grut_mcmc_relocation", "grut_mcmc_perturb",
@@ -304,6 +313,8 @@ def _declare(lib):
     lib.grt_stats.restype = C.c_int
     lib.grut_selective_adam_update.argtypes = [vp, C.POINTER(GrutAdamGroup), C.c_int, C.c_uint32, vp, C.c_int]
     lib.grut_selective_adam_update.restype = C.c_int
+    lib.grut_adam_update.argtypes = [vp, C.POINTER(GrutDenseAdamGroup), C.c_int, fp]
+    lib.grut_adam_update.restype = C.c_int
     lib.grut_pack_particles.argtypes = [vp, C.c_uint32, fp, fp, fp, fp, fp]
     lib.grut_pack_particles.restype = C.c_int
     lib.grut_unpack_particle_grads.argtypes = [vp, C.c_uint32] + [fp] * 5

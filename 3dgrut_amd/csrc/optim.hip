@@ -87,6 +87,72 @@ __global__ __launch_bounds__(kAdamThreads) void selective_adam_kernel(const Adam
     }
 }
 
+// ---- dense Adam: torch.optim.Adam(fused=True), every tensor of every parameter group in ONE launch ------------------------------
+// torch steps once per parameter group (each has its own lr): six multi-tensor launches and six step-counter launches per training
+// step of the reference's model (threedgrut/model/model.py:807-810).  Here the groups share the block-prefix table of the selective
+// kernel above.  The arithmetic is adam_math's (ATen/native/hip/fused_adam_utils.cuh) for fp32 tensors: the hyper-parameters are
+// double, so the moment updates are double statements rounded once, and the last statement is fp32.
+struct DenseAdamLaunch {
+    GrutDenseAdamGroup g[kAdamMaxGroups];
+    uint32_t block_end[kAdamMaxGroups];  // exclusive prefix of blocks per group
+    uint32_t slot[kAdamMaxGroups];       // the group's index in the caller's array: its two floats are scratch[2 slot], scratch[2 slot + 1]
+    int num_groups;
+};
+
+// One block per group, lane 0 works: the ONLY writer and reader of `step` in the call, so the streaming launch behind it (same stream)
+// cannot race with the increment, and the double pow / sqrt / division stay out of the 28 B-per-element pass.
+__global__ __launch_bounds__(64) void dense_adam_prologue_kernel(const DenseAdamLaunch L, float* __restrict__ scratch) {
+    if (threadIdx.x != 0) return;
+    const GrutDenseAdamGroup& G = L.g[blockIdx.x];
+    const float step = *G.step + 1.0f;
+    *G.step = step;
+    const float bc1 = (float)(1.0 - pow(G.beta1, (double)step));
+    const float bc2s = (float)sqrt(1.0 - pow(G.beta2, (double)step));
+    scratch[2u * L.slot[blockIdx.x]] = (float)(G.lr / (double)bc1);   // step_size: bc1 has no other use
+    scratch[2u * L.slot[blockIdx.x] + 1u] = bc2s;
+}
+
+__device__ __forceinline__ void dense_adam_element(float& p, float g, float& m, float& v, double b1, double b2, double eps, double wd,
+                                                   float step_size, float bc2s) {
+    if (wd != 0.0) g = (float)((double)g + (double)p * wd);
+    m = (float)(b1 * (double)m + (1.0 - b1) * (double)g);
+    v = (float)(b2 * (double)v + (1.0 - b2) * (double)g * (double)g);
+    const float denom = (float)((double)(sqrtf(v) / bc2s) + eps);
+    p -= step_size * m / denom;
+}
+
+__global__ __launch_bounds__(kAdamThreads) void dense_adam_kernel(const DenseAdamLaunch L, const float* __restrict__ scratch) {
+    int gi = 0;
+    while (gi + 1 < L.num_groups && blockIdx.x >= L.block_end[gi]) ++gi;
+    const GrutDenseAdamGroup G = L.g[gi];
+    const uint32_t first_block = gi == 0 ? 0u : L.block_end[gi - 1];
+    // block-uniform and ahead of every store of this kernel, so that they stay scalar loads
+    const float step_size = scratch[2u * L.slot[gi]], bc2s = scratch[2u * L.slot[gi] + 1u];
+    const uint64_t base = ((uint64_t)(blockIdx.x - first_block) * kAdamThreads + threadIdx.x) * 4ull;
+    if (base >= G.numel) return;
+    if (G.numel - base >= 4ull) {
+        float4 p = *reinterpret_cast<const float4*>(G.param + base);
+        const float4 g = *reinterpret_cast<const float4*>(G.grad + base);
+        float4 m = *reinterpret_cast<const float4*>(G.exp_avg + base);
+        float4 v = *reinterpret_cast<const float4*>(G.exp_avg_sq + base);
+        dense_adam_element(p.x, g.x, m.x, v.x, G.beta1, G.beta2, G.eps, G.weight_decay, step_size, bc2s);
+        dense_adam_element(p.y, g.y, m.y, v.y, G.beta1, G.beta2, G.eps, G.weight_decay, step_size, bc2s);
+        dense_adam_element(p.z, g.z, m.z, v.z, G.beta1, G.beta2, G.eps, G.weight_decay, step_size, bc2s);
+        dense_adam_element(p.w, g.w, m.w, v.w, G.beta1, G.beta2, G.eps, G.weight_decay, step_size, bc2s);
+        *reinterpret_cast<float4*>(G.param + base) = p;
+        *reinterpret_cast<float4*>(G.exp_avg + base) = m;
+        *reinterpret_cast<float4*>(G.exp_avg_sq + base) = v;
+    } else {   // the group's last 1-3 elements
+        for (uint64_t e = base; e < G.numel; ++e) {
+            float p = G.param[e], m = G.exp_avg[e], v = G.exp_avg_sq[e];
+            dense_adam_element(p, G.grad[e], m, v, G.beta1, G.beta2, G.eps, G.weight_decay, step_size, bc2s);
+            G.param[e] = p;
+            G.exp_avg[e] = m;
+            G.exp_avg_sq[e] = v;
+        }
+    }
+}
+
 // ---- parameter marshalling ---------------------------------------------------------------------
 // The renderers consume ParticleDensity rows {position, density, quaternion, scale, pad} (48 B); the model keeps the four
 // tensors apart and the reference's plugin concatenates them with torch.cat every call (threedgut_tracer/tracer.py:178,
@@ -272,6 +338,52 @@ extern "C" int grut_selective_adam_update(void* stream, const GrutAdamGroup* gro
         first = i;
         if (L.num_groups == 0) continue;
         hipLaunchKernelGGL(selective_adam_kernel, dim3((uint32_t)blocks), dim3(kAdamThreads), 0, reinterpret_cast<hipStream_t>(stream), L);
+        GRUT_HIP(hipGetLastError());
+    }
+    return GRUT_OK;
+}
+
+extern "C" int grut_adam_update(void* stream, const GrutDenseAdamGroup* groups, int num_groups, float* scratch) {
+    using namespace grut;
+    GRUT_REQUIRE(num_groups >= 0, "grut_adam_update: num_groups %d is negative", num_groups);
+    GRUT_REQUIRE(num_groups == 0 || groups, "grut_adam_update: groups is NULL");
+    GRUT_REQUIRE(scratch, "grut_adam_update: scratch is NULL");
+    uint64_t all_blocks = 0;
+    for (int i = 0; i < num_groups; ++i) {   // every check before the first launch
+        const GrutDenseAdamGroup& g = groups[i];
+        if (g.numel == 0) continue;
+        GRUT_REQUIRE(g.param, "grut_adam_update: group %d: param is NULL", i);
+        GRUT_REQUIRE(g.grad, "grut_adam_update: group %d: grad is NULL", i);
+        GRUT_REQUIRE(g.exp_avg, "grut_adam_update: group %d: exp_avg is NULL", i);
+        GRUT_REQUIRE(g.exp_avg_sq, "grut_adam_update: group %d: exp_avg_sq is NULL", i);
+        GRUT_REQUIRE(g.step, "grut_adam_update: group %d: step is NULL", i);
+        GRUT_REQUIRE((uintptr_t)g.param % 16 == 0, "grut_adam_update: group %d: param must be 16-byte aligned", i);
+        GRUT_REQUIRE((uintptr_t)g.grad % 16 == 0, "grut_adam_update: group %d: grad must be 16-byte aligned", i);
+        GRUT_REQUIRE((uintptr_t)g.exp_avg % 16 == 0, "grut_adam_update: group %d: exp_avg must be 16-byte aligned", i);
+        GRUT_REQUIRE((uintptr_t)g.exp_avg_sq % 16 == 0, "grut_adam_update: group %d: exp_avg_sq must be 16-byte aligned", i);
+        GRUT_REQUIRE(g.numel < (1ull << 48), "grut_adam_update: group %d: numel is too large", i);
+        all_blocks += ((g.numel + 3) / 4 + kAdamThreads - 1) / kAdamThreads;
+        GRUT_REQUIRE(all_blocks < 0x7FFFFFFFull, "grut_adam_update: too many elements for one grid (numel of groups 0..%d)", i);
+    }
+    for (int first = 0; first < num_groups;) {  // batches of kAdamMaxGroups non-empty groups, as grut_selective_adam_update
+        DenseAdamLaunch L{};
+        uint64_t blocks = 0;
+        int i = first;
+        for (; i < num_groups && L.num_groups < kAdamMaxGroups; ++i) {
+            const GrutDenseAdamGroup& g = groups[i];
+            if (g.numel == 0) continue;
+            blocks += ((g.numel + 3) / 4 + kAdamThreads - 1) / kAdamThreads;
+            L.g[L.num_groups] = g;
+            L.block_end[L.num_groups] = (uint32_t)blocks;
+            L.slot[L.num_groups] = (uint32_t)i;
+            ++L.num_groups;
+        }
+        first = i;
+        if (L.num_groups == 0) continue;
+        hipLaunchKernelGGL(dense_adam_prologue_kernel, dim3((uint32_t)L.num_groups), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), L, scratch);
+        GRUT_HIP(hipGetLastError());
+        hipLaunchKernelGGL(dense_adam_kernel, dim3((uint32_t)blocks), dim3(kAdamThreads), 0, reinterpret_cast<hipStream_t>(stream), L,
+                           static_cast<const float*>(scratch));
         GRUT_HIP(hipGetLastError());
     }
     return GRUT_OK;

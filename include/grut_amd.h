@@ -1019,6 +1019,34 @@ enum { GRUT_VIS_NONE = 0,        /* every row is updated */
 int grut_selective_adam_update(void* stream, const GrutAdamGroup* groups, int num_groups, uint32_t num_rows,
                                const void* visibility, int visibility_kind);
 
+/* One tensor of the dense Adam update: what torch.optim.Adam(fused=True) keeps per parameter.  param / grad / exp_avg / exp_avg_sq
+ * are contiguous fp32 DEVICE arrays of `numel` elements with 16-byte aligned bases; `step` is the DEVICE fp32 scalar torch keeps with
+ * fused=True.  Hyper-parameters travel as double, as torch hands them to its kernel. */
+typedef struct GrutDenseAdamGroup {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    float* step;
+    uint64_t numel;
+    double lr, beta1, beta2, eps, weight_decay;
+} GrutDenseAdamGroup;
+/* torch's fused Adam (no amsgrad, no maximize, no grad scaler, weight decay coupled) over ALL groups in one launch.  Statement order and
+ * roundings of adam_math / FusedAdamMathFunctor (ATen/native/hip/fused_adam_utils.cuh), fp32 tensors:
+ *   step += 1 (fp32);  bc1 = (float)(1 - pow(beta1, step)),  bc2s = (float)sqrt(1 - pow(beta2, step))   (pow and sqrt in double)
+ *   g = (float)(g + p * weight_decay) when weight_decay != 0 (double);
+ *   m = (float)(beta1 m + (1 - beta1) g);  v = (float)(beta2 v + (1 - beta2) g g)                     (double, one rounding each)
+ *   step_size = (float)(lr / bc1) (double division);  denom = (float)(sqrtf(v) / bc2s + eps) (fp32 sqrt and division, double addition)
+ *   p -= step_size * m / denom                                                                          (fp32, correctly rounded)
+ * A prologue launch of one thread per group increments `step` and leaves {step_size, bc2s} of group i in scratch[2 i], scratch[2 i + 1]
+ * (bc1 is used by step_size alone, so the quotient is stored in its place); the streaming launch reads the two floats and never
+ * touches `step`, so no workgroup races with the increment.  scratch: [num_groups, 2] fp32 DEVICE, contents arbitrary before and
+ * unspecified after.  A group with numel == 0 is skipped and its `step` stays.  Two launches per batch of 8 non-empty groups, no
+ * atomics (equal inputs give equal bits), no allocation, no synchronisation, every launch on `stream`.
+ * GRUT_ERR_BAD_INPUT before any HIP call: groups NULL with num_groups > 0, num_groups < 0, scratch NULL, and for a group with
+ * numel > 0 a NULL pointer or a tensor base that is not 16-byte aligned. */
+int grut_adam_update(void* stream, const GrutDenseAdamGroup* groups, int num_groups, float* scratch);
+
 /* human-readable text of the last error raised on the calling thread */
 const char* grut_last_error(void);
 /* ABI version; bumped whenever a struct above changes */
