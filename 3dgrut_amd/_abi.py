@@ -186,7 +186,7 @@ EXPORTED_SYMBOLS = [
     "gut_create", "gut_destroy", "gut_forward", "gut_backward", "gut_backward_unpacked", "gut_forward_split", "gut_backward_split", "gut_backward_unpacked_split", "gut_backward_factored", "gut_backward_factored_chunked", "grut_sph_grad_from_views", "gut_timings", "gut_stats",
     "gut_profile_enable", "gut_profile_select", "gut_profile_read",
     "gut_debug_fetch", "gut_debug_fetch_work", "grut_debug_pose_from_c2w", "grut_debug_frame_poses", "grut_sort_pairs_u32", "grut_sort_scratch_bytes", "grut_inclusive_scan_u32",
-    "grut_scan_scratch_bytes", "grut_debug_sort_pairs_u32", "grut_debug_scan_gather_u32", "gut_debug_tile_ranges", "grt_debug_list_ranges",
+    "grut_scan_scratch_bytes", "grut_debug_sort_pairs_u32", "grut_debug_sort_pairs_u32_tiled", "grut_debug_scan_gather_u32", "gut_debug_tile_ranges", "grt_debug_list_ranges",
     "grt_create", "grt_destroy", "grt_build_bvh", "grt_forward", "grt_backward", "grt_timings", "grt_stats", "grt_debug_fetch_work",
     "grt_debug_forward_hits", "grt_debug_fetch_instances", "grt_debug_fetch_custom_boxes", "grt_debug_fetch_lists", "grt_debug_backward_signature", "grt_build_mesh_bvh", "grt_trace_hybrid",
     "grut_selective_adam_update", "grut_adam_update", "grut_pack_particles", "grut_unpack_particle_grads", "grut_activate_pack", "grut_activate_pack_backward",
@@ -268,6 +268,10 @@ def _declare(lib):
     lib.grut_debug_sort_pairs_u32.argtypes = [vp, C.c_uint32, up, C.c_int, C.c_int, up, up, up, up, C.c_int, vp, C.c_uint64,
                                               C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     lib.grut_debug_sort_pairs_u32.restype = C.c_int
+    # the same with tile_keys (2048 / 4096 / 8192 / 16384, 0 = automatic) behind values_iota
+    lib.grut_debug_sort_pairs_u32_tiled.argtypes = [vp, C.c_uint32, up, C.c_int, C.c_int, up, up, up, up, C.c_int, C.c_uint32, vp, C.c_uint64,
+                                                    C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.grut_debug_sort_pairs_u32_tiled.restype = C.c_int
     lib.grut_debug_scan_gather_u32.argtypes = [vp, C.c_uint32, up, up, up, vp, C.c_uint64]
     lib.grut_debug_scan_gather_u32.restype = C.c_int
     # stream, n, n_dev, tile_mask, num_tiles, sorted keys, ranges, boundary_tile, the segment length (host, out)

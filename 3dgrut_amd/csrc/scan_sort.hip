@@ -27,15 +27,16 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane) {
     return v;
 }
 
-// block-wide exclusive scan of one value per thread (256 threads); returns exclusive prefix, *total = block sum
-__device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t* total, uint32_t* s_wave /*[4]*/) {
+// block-wide exclusive scan of one value per thread (THREADS threads); returns exclusive prefix, *total = block sum
+template <int THREADS>
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* total, uint32_t* s_wave /*[THREADS / 64]*/) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t incl = wave_incl_scan_u32(v, lane);
     if (lane == 63) s_wave[wave] = incl;
     __syncthreads();
     uint32_t base = 0, tot = 0;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) {
+    for (int w = 0; w < THREADS / 64; ++w) {
         const uint32_t s = s_wave[w];
         if (w < wave) base += s;
         tot += s;
@@ -43,6 +44,9 @@ __device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t* to
     *total = tot;
     __syncthreads();
     return base + incl - v;
+}
+__device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t* total, uint32_t* s_wave /*[4]*/) {
+    return block_excl_scan<256>(v, total, s_wave);
 }
 
 __device__ __forceinline__ void load_items(const uint32_t* __restrict__ in, const uint32_t* __restrict__ gather,
@@ -166,9 +170,23 @@ constexpr int kSortThreads = 256;
 #ifndef GRUT_SORT_SMALL
 #define GRUT_SORT_SMALL 8
 #endif
-constexpr int kSortRoundsLarge = 16, kSortRoundsSmall = GRUT_SORT_SMALL;
+constexpr int kSortRoundsLarge = 16, kSortRoundsSmall = GRUT_SORT_SMALL;   // (the one-sweep passes' two tiles)
 constexpr uint32_t kSortSmallLimit = 2u << 20;
 constexpr int kRadix       = 256;
+
+// Tile geometries of the three-kernel passes: threads x keys per lane.  A larger tile makes a (tile, digit) run of the scatter longer (fewer
+// partial cache lines per output array) and the histogram matrix smaller; LDS per workgroup is about 9 bytes per key.
+enum SortGeom { kGeom2048 = 0, kGeom4096, kGeom8192, kGeom16384, kNumSortGeoms };
+constexpr uint32_t kGeomTile[kNumSortGeoms] = {256u * 8u, 256u * 16u, 512u * 16u, 1024u * 16u};
+// Chosen per array size from measurements (profiles/sort_tiles_ab.json, sort_tiles_after.txt): up to 2 M keys 2048-key tiles (1 M depth keys:
+// 74 us against 80 / 88 / 110 us with 4096 / 8192 / 16384); above, 8192-key tiles: the 1 M-particle 1080p frame is 0.007 ms faster with them
+// than with 4096 (its 11.5 M pairs sort in the same time), the 3 M-particle frame 0.036 ms (tile sort 0.200 against 0.220 ms), the 3DGRT
+// frame with its list sorts 0.09 ms.  16384-key tiles (one workgroup per CU) lose at every size.
+inline int pick_sort_geom(uint32_t n) { return n <= kSortSmallLimit ? (int)kGeom2048 : (int)kGeom8192; }
+// rows of the digit-major histogram matrix start on 16 bytes: the row scan moves them as uint4
+__host__ __device__ inline uint32_t hist_row_stride(uint32_t nb) { return (nb + 3u) & ~3u; }
+// workgroups of a pass (in 64 bits: n + tile - 1 may not fit 32)
+inline uint32_t sort_tiles(uint32_t n, uint32_t tile) { return (uint32_t)(((uint64_t)n + tile - 1u) / tile); }
 
 __device__ __forceinline__ uint32_t eff_count(uint32_t n, const uint32_t* n_dev) {
     if (!n_dev) return n;
@@ -176,106 +194,158 @@ __device__ __forceinline__ uint32_t eff_count(uint32_t n, const uint32_t* n_dev)
     return m < n ? m : n;
 }
 
-// histogram matrix is digit-major: hist[d * nb + b]
-template <int kSortRounds>
-__global__ __launch_bounds__(kSortThreads) void radix_hist_kernel(const uint32_t* __restrict__ keys, uint32_t n,
-                                                                  const uint32_t* __restrict__ n_dev, int shift, uint32_t mask,
-                                                                  uint32_t nb, uint32_t* __restrict__ hist) {
-    __shared__ uint32_t s_hist[4][kRadix];
-    const int wave = threadIdx.x >> 6;
+// histogram matrix is digit-major: hist[d * stride + b], stride = hist_row_stride(nb); only the 2^nbits rows of digits that can occur
+// are written, scanned and read
+template <int THREADS, int ROUNDS>
+__global__ __launch_bounds__(THREADS) void radix_hist_kernel(const uint32_t* __restrict__ keys, uint32_t n,
+                                                             const uint32_t* __restrict__ n_dev, int shift, int nbits,
+                                                             uint32_t stride, uint32_t* __restrict__ hist) {
+    constexpr int kCopies = 4;   // waves share the copies round robin (one per wave at 256 threads)
+    __shared__ uint32_t s_hist[kCopies][kRadix];
+    const int copy = (threadIdx.x >> 6) & (kCopies - 1);
     const uint32_t ne = eff_count(n, n_dev);
-#pragma unroll
-    for (int w = 0; w < 4; ++w) s_hist[w][threadIdx.x] = 0;
-    __syncthreads();
-    constexpr int kSortTile = kSortThreads * kSortRounds;
+    const uint32_t mask = (1u << nbits) - 1u;
+    constexpr int kSortTile = THREADS * ROUNDS;
     const uint32_t base = blockIdx.x * kSortTile;
-    if (base < ne) {
-        // 16 B per lane, 4 loads per thread
+    if (base >= ne) return;   // a tile behind the live count: the row scan and the scatter stop in front of its column
+    for (int i = threadIdx.x; i < kCopies * kRadix; i += THREADS) (&s_hist[0][0])[i] = 0;
+    __syncthreads();
+    // 16 B per lane, ROUNDS / 4 loads per thread
 #pragma unroll
-        for (int k = 0; k < kSortRounds / 4; ++k) {
-            const uint32_t i = base + (k * kSortThreads + threadIdx.x) * 4;
-            if (i + 4 <= ne) {
-                const uint4 v = *reinterpret_cast<const uint4*>(keys + i);
-                atomicAdd(&s_hist[wave][(v.x >> shift) & mask], 1u);
-                atomicAdd(&s_hist[wave][(v.y >> shift) & mask], 1u);
-                atomicAdd(&s_hist[wave][(v.z >> shift) & mask], 1u);
-                atomicAdd(&s_hist[wave][(v.w >> shift) & mask], 1u);
-            } else {
-                for (uint32_t j = i; j < ne && j < i + 4; ++j) atomicAdd(&s_hist[wave][(keys[j] >> shift) & mask], 1u);
-            }
+    for (int k = 0; k < ROUNDS / 4; ++k) {
+        const uint32_t i = base + (k * THREADS + threadIdx.x) * 4;
+        if (i + 4 <= ne) {
+            const uint4 v = *reinterpret_cast<const uint4*>(keys + i);
+            atomicAdd(&s_hist[copy][(v.x >> shift) & mask], 1u);
+            atomicAdd(&s_hist[copy][(v.y >> shift) & mask], 1u);
+            atomicAdd(&s_hist[copy][(v.z >> shift) & mask], 1u);
+            atomicAdd(&s_hist[copy][(v.w >> shift) & mask], 1u);
+        } else {
+            for (uint32_t j = i; j < ne && j < i + 4; ++j) atomicAdd(&s_hist[copy][(keys[j] >> shift) & mask], 1u);
         }
     }
     __syncthreads();
     const uint32_t d = threadIdx.x;
-    hist[(size_t)d * nb + blockIdx.x] = s_hist[0][d] + s_hist[1][d] + s_hist[2][d] + s_hist[3][d];
+    if (d <= mask) hist[(size_t)d * stride + blockIdx.x] = s_hist[0][d] + s_hist[1][d] + s_hist[2][d] + s_hist[3][d];
 }
 
-// Exclusive scan of each digit's row of per-block counts (in place) + the digit totals: with the 256-entry scan of the
-// totals done inside the scatter kernel this replaces a generic three-kernel scan of the whole matrix per pass.
-// One workgroup per digit that can occur (2^nbits of them: the rows of the other digits are all zero and stay untouched; their totals
-// are zeroed by workgroup 0).
-__global__ __launch_bounds__(kSortThreads) void radix_rowscan_kernel(uint32_t* __restrict__ hist, uint32_t nb, uint32_t* __restrict__ totals) {
+// Exclusive scan of each digit's row of per-block counts (in place) + the digit totals: with the scan of the totals done inside the
+// scatter kernel this replaces a generic three-kernel scan of the whole matrix per pass.
+// One workgroup per digit that can occur (2^nbits of them).  A thread owns a contiguous piece of the row and issues every load of it
+// before the first add, so a row of up to kRowChunk counts costs one round trip to memory and one block scan, not one per 256 counts.
+constexpr int kRowThreads = 256, kRowVecs = 8;                    // 8 x uint4 = 32 counts per thread
+constexpr uint32_t kRowChunk = kRowThreads * kRowVecs * 4;         // 8192 counts per block scan
+// Only the columns of tiles that hold live pairs are scanned (n_dev: the tiles behind the count wrote nothing and read nothing).  The
+// last uint4 of a row may reach up to 3 columns past the live tiles and leaves running sums there: those columns belong to skipped tiles,
+// which holds in every kernel of every pass because *n_dev does not change while a sort runs.
+__global__ __launch_bounds__(kRowThreads) void radix_rowscan_kernel(uint32_t* __restrict__ hist, uint32_t n, const uint32_t* __restrict__ n_dev,
+                                                                    uint32_t tile, uint32_t stride, uint32_t* __restrict__ totals) {
     __shared__ uint32_t s_wave[4];
-    if (blockIdx.x == 0 && threadIdx.x >= gridDim.x) totals[threadIdx.x] = 0u;
-    uint32_t* row = hist + (size_t)blockIdx.x * nb;
+    const uint32_t ne = eff_count(n, n_dev);
+    const uint32_t nb = ne / tile + (ne % tile != 0u ? 1u : 0u);
+    uint32_t* row = hist + (size_t)blockIdx.x * stride;
     uint32_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += kSortThreads) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < nb ? row[i] : 0u;
+    for (uint32_t base = 0; base < nb; base += kRowChunk) {
+        const uint32_t len = min(kRowChunk, nb - base);
+        // uint4s per thread in this chunk (wave-uniform): the threads' pieces are contiguous and cover [base, base + len)
+        const uint32_t vecs = (len + kRowThreads * 4 - 1) / (kRowThreads * 4);
+        const uint32_t i0 = base + threadIdx.x * vecs * 4;
+        uint4 x[kRowVecs];
+#pragma unroll
+        for (int k = 0; k < kRowVecs; ++k) {
+            const uint32_t i = i0 + k * 4;
+            x[k] = make_uint4(0u, 0u, 0u, 0u);
+            // (the row is padded to a multiple of 4 words: a uint4 that begins inside the row ends inside its padding at the latest)
+            if ((uint32_t)k < vecs && i < nb) x[k] = *reinterpret_cast<const uint4*>(row + i);
+        }
+        uint32_t s = 0;
+#pragma unroll
+        for (int k = 0; k < kRowVecs; ++k) {
+            const uint32_t i = i0 + k * 4;
+            // words of the padding hold whatever the scratch held: they do not count
+            if (i + 1 >= nb) x[k].y = 0u;
+            if (i + 2 >= nb) x[k].z = 0u;
+            if (i + 3 >= nb) x[k].w = 0u;
+            s += x[k].x + x[k].y + x[k].z + x[k].w;
+        }
         uint32_t total;
-        const uint32_t excl = block_excl_scan_256(v, &total, s_wave);
-        if (i < nb) row[i] = carry + excl;
+        uint32_t run = carry + block_excl_scan<kRowThreads>(s, &total, s_wave);
+#pragma unroll
+        for (int k = 0; k < kRowVecs; ++k) {
+            const uint32_t i = i0 + k * 4;
+            uint4 y;
+            y.x = run; run += x[k].x;
+            y.y = run; run += x[k].y;
+            y.z = run; run += x[k].z;
+            y.w = run; run += x[k].w;
+            if ((uint32_t)k < vecs && i < nb) *reinterpret_cast<uint4*>(row + i) = y;   // (the padding words behind nb get the total: never read)
+        }
         carry += total;
     }
     if (threadIdx.x == 0) totals[blockIdx.x] = carry;
 }
 
-template <int kSortRounds>
-__global__ __launch_bounds__(kSortThreads) void radix_scatter_kernel(const uint32_t* __restrict__ keys_in,
-                                                                     const uint32_t* __restrict__ vals_in, uint32_t n,
-                                                                     const uint32_t* __restrict__ n_dev, int shift, uint32_t mask,
-                                                                     uint32_t nb, const uint32_t* __restrict__ hist_scanned,
-                                                                     const uint32_t* __restrict__ digit_totals,
-                                                                     uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out) {
-    constexpr int kSortTile = kSortThreads * kSortRounds, kSortWaveKeys = 64 * kSortRounds;
+// BALLOTS: ballots per key of the wave64 match, a compile-time bound >= nbits (with nbits as a run-time bound the compiler evaluates the
+// wave-uniform conditions on the VALU and branches around every ballot; a ballot over a bit above the digit is all zeros and changes nothing)
+template <int THREADS, int ROUNDS, int BALLOTS>
+__global__ __launch_bounds__(THREADS) void radix_scatter_kernel(const uint32_t* __restrict__ keys_in,
+                                                                const uint32_t* __restrict__ vals_in, uint32_t n,
+                                                                const uint32_t* __restrict__ n_dev, int shift, int nbits,
+                                                                uint32_t stride, const uint32_t* __restrict__ hist_scanned,
+                                                                const uint32_t* __restrict__ digit_totals,
+                                                                uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out) {
+    constexpr int kWaves = THREADS / 64, kSortTile = THREADS * ROUNDS, kSortWaveKeys = 64 * ROUNDS;
     // per-wave digit counters; after the ranking phase they are turned into global scatter bases
-    __shared__ uint32_t s_cnt[4][kRadix];
+    __shared__ uint32_t s_cnt[kWaves][kRadix];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t ne = eff_count(n, n_dev);
     const uint32_t base = blockIdx.x * kSortTile;
     if (base >= ne) return;
+    const uint32_t mask = (1u << nbits) - 1u;
+    // thread d < 2^nbits owns digit d (a workgroup may have more threads than there are digits: the others carry zeros through the
+    // scans).  Its two words of the scanned histogram are fetched here, long before they are needed.
+    const bool owner = threadIdx.x <= mask;
+    const uint32_t my_total = owner ? digit_totals[threadIdx.x] : 0u;
+    const uint32_t my_before = owner ? hist_scanned[(size_t)threadIdx.x * stride + blockIdx.x] : 0u;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) s_cnt[w][threadIdx.x] = 0;
+    for (int w = 0; w < kWaves * kRadix / THREADS; ++w) (&s_cnt[0][0])[w * THREADS + threadIdx.x] = 0;
     __syncthreads();
 
-    uint32_t key[kSortRounds], val[kSortRounds], rank[kSortRounds];
+    uint32_t key[ROUNDS], val[ROUNDS], rank[ROUNDS];
     const uint32_t wbase = base + wave * kSortWaveKeys;
-    volatile uint32_t* cnt = s_cnt[wave];
+    // the wave's own counters: relaxed wavefront-scope atomics on the LDS array itself keep the accesses ds_read / ds_write in program
+    // order (through a volatile pointer they become flat loads and stores with a wait on the vector memory counter after each)
+    uint32_t* cnt = s_cnt[wave];
 #pragma unroll
-    for (int r = 0; r < kSortRounds; ++r) {
+    for (int r = 0; r < ROUNDS; ++r) {
         const uint32_t i = wbase + r * 64 + lane;
         const bool valid = i < ne;
         key[r] = valid ? keys_in[i] : 0xFFFFFFFFu;
         val[r] = valid ? (vals_in ? vals_in[i] : i) : 0u;   // vals_in == nullptr: the values are the positions themselves (first pass of an iota payload)
     }
 #pragma unroll
-    for (int r = 0; r < kSortRounds; ++r) {
+    for (int r = 0; r < ROUNDS; ++r) {
         const uint32_t i = wbase + r * 64 + lane;
         const bool valid = i < ne;
         const uint32_t d = (key[r] >> shift) & mask;
-        // lanes holding the same digit (wave64 match via 8 ballots)
-        unsigned long long m = __ballot(valid);
+        // lanes holding the same digit (wave64 match via one ballot per bit of the digit).  Per bit, `same` is all ones in the lanes whose
+        // bit is set: a lane keeps the ballot's lanes where its own bit is set and the other lanes where it is not, m &= ~(ballot ^ same)
+        // on each 32-bit half (5 VALU instructions per ballot; the select on 64-bit masks `bit ? ballot : ~ballot` compiles to 9)
+        const unsigned long long mv = __ballot(valid);
+        uint32_t mlo = (uint32_t)mv, mhi = (uint32_t)(mv >> 32);
 #pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const unsigned long long bb = __ballot((d >> b) & 1u);
-            m &= ((d >> b) & 1u) ? bb : ~bb;
+        for (int b = 0; b < BALLOTS; ++b) {
+            const uint32_t same = (uint32_t)__builtin_amdgcn_sbfe((int)d, b, 1);
+            const unsigned long long bb = __ballot(same != 0u);
+            mlo &= ~((uint32_t)bb ^ same);
+            mhi &= ~((uint32_t)(bb >> 32) ^ same);
         }
-        const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        const uint32_t count  = (uint32_t)__popcll(m);
+        const uint32_t before = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));
+        const uint32_t count  = (uint32_t)(__popc(mlo) + __popc(mhi));
         uint32_t old = 0;
-        if (valid) old = cnt[d];
+        if (valid) old = __hip_atomic_load(&cnt[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         __builtin_amdgcn_wave_barrier();
-        if (valid && before == 0) cnt[d] = old + count;
+        if (valid && before == 0) __hip_atomic_store(&cnt[d], old + count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         __builtin_amdgcn_wave_barrier();
         rank[r] = old + before;
     }
@@ -285,25 +355,31 @@ __global__ __launch_bounds__(kSortThreads) void radix_scatter_kernel(const uint3
     __shared__ uint32_t s_keys[kSortTile], s_vals[kSortTile];
     __shared__ uint32_t s_dstart[kRadix];  // first slot of digit d in the block-sorted order
     __shared__ uint32_t s_gdelta[kRadix];  // (global base of (digit, block)) - s_dstart[d]
-    __shared__ uint32_t s_wave_tot[4];
+    __shared__ uint32_t s_wave_tot[kWaves];
     {
         const uint32_t d = threadIdx.x;
         uint32_t run = 0;
+        if (owner) {
+            uint32_t c[kWaves];
 #pragma unroll
-        for (int w = 0; w < 4; ++w) {  // exclusive prefix of digit d over the 4 waves
-            const uint32_t c = s_cnt[w][d];
-            s_cnt[w][d] = run;
-            run += c;
+            for (int w = 0; w < kWaves; ++w) c[w] = s_cnt[w][d];
+#pragma unroll
+            for (int w = 0; w < kWaves; ++w) {  // exclusive prefix of digit d over the waves
+                s_cnt[w][d] = run;
+                run += c[w];
+            }
         }
         uint32_t total;
-        const uint32_t excl = block_excl_scan_256(run, &total, s_wave_tot);
-        const uint32_t digit_base = block_excl_scan_256(digit_totals[d], &total, s_wave_tot);  // keys with a smaller digit, all blocks
-        s_dstart[d] = excl;
-        s_gdelta[d] = digit_base + hist_scanned[(size_t)d * nb + blockIdx.x] - excl;
+        const uint32_t excl = block_excl_scan<THREADS>(run, &total, s_wave_tot);
+        const uint32_t digit_base = block_excl_scan<THREADS>(my_total, &total, s_wave_tot);  // keys with a smaller digit, all blocks
+        if (owner) {
+            s_dstart[d] = excl;
+            s_gdelta[d] = digit_base + my_before - excl;
+        }
     }
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < kSortRounds; ++r) {
+    for (int r = 0; r < ROUNDS; ++r) {
         const uint32_t i = wbase + r * 64 + lane;
         if (i < ne) {
             const uint32_t d = (key[r] >> shift) & mask;
@@ -315,8 +391,8 @@ __global__ __launch_bounds__(kSortThreads) void radix_scatter_kernel(const uint3
     __syncthreads();
     const uint32_t nvalid = min((uint32_t)kSortTile, ne - base);
 #pragma unroll
-    for (int r = 0; r < kSortRounds; ++r) {
-        const uint32_t idx = r * kSortThreads + threadIdx.x;
+    for (int r = 0; r < ROUNDS; ++r) {
+        const uint32_t idx = r * THREADS + threadIdx.x;
         if (idx < nvalid) {
             const uint32_t k = s_keys[idx];
             const uint32_t dst = s_gdelta[(k >> shift) & mask] + idx;
@@ -324,6 +400,19 @@ __global__ __launch_bounds__(kSortThreads) void radix_scatter_kernel(const uint3
             vals_out[dst] = s_vals[idx];
         }
     }
+}
+
+// one pass of the three-kernel formulation with the tile geometry as a compile-time pair
+template <int THREADS, int ROUNDS>
+void launch_sort_pass(hipStream_t s, uint32_t n, const uint32_t* n_dev, int bit, int nbits, uint32_t nb, uint32_t* hist, uint32_t* totals,
+                      const uint32_t* ki, const uint32_t* vin, uint32_t* ko, uint32_t* vo) {
+    const uint32_t stride = hist_row_stride(nb);
+    hipLaunchKernelGGL((radix_hist_kernel<THREADS, ROUNDS>), dim3(nb), dim3(THREADS), 0, s, ki, n, n_dev, bit, nbits, stride, hist);
+    hipLaunchKernelGGL(radix_rowscan_kernel, dim3(1u << nbits), dim3(kRowThreads), 0, s, hist, n, n_dev, (uint32_t)(THREADS * ROUNDS), stride, totals);
+    // (the tile passes of a 1080p frame have 7- and 6-bit digits, the depth passes 8-bit ones)
+    if (nbits <= 6) hipLaunchKernelGGL((radix_scatter_kernel<THREADS, ROUNDS, 6>), dim3(nb), dim3(THREADS), 0, s, ki, vin, n, n_dev, bit, nbits, stride, hist, totals, ko, vo);
+    else if (nbits == 7) hipLaunchKernelGGL((radix_scatter_kernel<THREADS, ROUNDS, 7>), dim3(nb), dim3(THREADS), 0, s, ki, vin, n, n_dev, bit, nbits, stride, hist, totals, ko, vo);
+    else hipLaunchKernelGGL((radix_scatter_kernel<THREADS, ROUNDS, 8>), dim3(nb), dim3(THREADS), 0, s, ki, vin, n, n_dev, bit, nbits, stride, hist, totals, ko, vo);
 }
 
 
@@ -515,10 +604,12 @@ int inclusive_scan_u32(hipStream_t s, uint32_t n, const uint32_t* in, const uint
 constexpr size_t kOnesweepHead = (size_t)kMaxPasses * kRadix + 64;
 static bool sort_legacy();
 size_t sort_scratch_bytes(uint32_t n) {
-    const uint32_t nb = div_up(n, (uint32_t)(kSortThreads * kSortRoundsSmall));   // (the smaller tile: an upper bound for either layout)
-    const size_t hist = (size_t)kRadix * nb * sizeof(uint32_t);
+    // the smallest tile has the most workgroups and so the largest histogram matrix: an upper bound for every geometry and either layout
+    const uint32_t nb = sort_tiles(n, kGeomTile[kGeom2048]);
+    const size_t hist = (size_t)kRadix * hist_row_stride(nb) * sizeof(uint32_t);
     const size_t legacy = hist + kRadix * sizeof(uint32_t) + 256;  // per-block digit counts + digit totals
-    const size_t onesweep = (kOnesweepHead + (size_t)kMaxPasses * nb * kRadix) * sizeof(uint32_t);
+    const uint32_t nb1 = sort_tiles(n, (uint32_t)(kSortThreads * kSortRoundsSmall));   // (the one-sweep passes' own smaller tile)
+    const size_t onesweep = (kOnesweepHead + (size_t)kMaxPasses * nb1 * kRadix) * sizeof(uint32_t);
     // (the one-sweep layout is ~4x the three-kernel one: only handles that opted into it pay for it)
     return (sort_legacy() || legacy > onesweep) ? legacy : onesweep;
 }
@@ -533,23 +624,24 @@ static bool sort_legacy() {
     return v;
 }
 
-int sort_pairs_u32(hipStream_t s, uint32_t n, const uint32_t* n_dev, int begin_bit, int end_bit,
-                   uint32_t* keys, uint32_t* vals, uint32_t* keys_tmp, uint32_t* vals_tmp,
-                   void* scratch, size_t scratch_bytes, uint32_t** out_keys, uint32_t** out_vals, bool vals_iota) {
+// geom: one of SortGeom for the three-kernel passes whatever n is (the debug entry), or -1 for the host's choice
+static int sort_pairs_impl(hipStream_t s, uint32_t n, const uint32_t* n_dev, int begin_bit, int end_bit,
+                           uint32_t* keys, uint32_t* vals, uint32_t* keys_tmp, uint32_t* vals_tmp,
+                           void* scratch, size_t scratch_bytes, uint32_t** out_keys, uint32_t** out_vals, bool vals_iota, int geom) {
     *out_keys = keys;
     *out_vals = vals;
     if (n == 0 || end_bit <= begin_bit) return GRUT_OK;
     GRUT_REQUIRE(scratch_bytes >= sort_scratch_bytes(n), "sort scratch too small");
     // (the histogram kernels read whichever buffer holds a pass's input 16 bytes at a time)
     GRUT_REQUIRE(aligned16(keys) && aligned16(keys_tmp), "sort: keys and keys_tmp must be 16-byte aligned");
-    const bool small = n <= kSortSmallLimit;
-    const uint32_t nb = div_up(n, (uint32_t)(kSortThreads * (small ? kSortRoundsSmall : kSortRoundsLarge)));
+    GRUT_REQUIRE(aligned16(scratch), "sort: scratch must be 16-byte aligned");
     uint32_t* hist = reinterpret_cast<uint32_t*>(scratch);
-    uint32_t* totals = hist + (size_t)kRadix * nb;
     uint32_t *ki = keys, *vi = vals, *ko = keys_tmp, *vo = vals_tmp;
     {
         const int total_bits = end_bit - begin_bit, passes = (total_bits + 7) / 8, width = (total_bits + passes - 1) / passes;
-        if (!sort_legacy() && passes <= kMaxPasses) {
+        if (geom < 0 && !sort_legacy() && passes <= kMaxPasses) {
+            const bool small = n <= kSortSmallLimit;
+            const uint32_t nb = div_up(n, (uint32_t)(kSortThreads * (small ? kSortRoundsSmall : kSortRoundsLarge)));
             uint32_t* head = reinterpret_cast<uint32_t*>(scratch);
             uint32_t* tickets = head + (size_t)kMaxPasses * kRadix;
             uint32_t* status = head + kOnesweepHead;
@@ -575,16 +667,19 @@ int sort_pairs_u32(hipStream_t s, uint32_t n, const uint32_t* n_dev, int begin_b
         }
     }
     // digits of equal width: 13 tile bits are sorted as 7 + 6, not 8 + 5 — the row scan works on 128 + 64 rows instead of 256 + 256
+    if (geom < 0) geom = pick_sort_geom(n);
+    const uint32_t nb = sort_tiles(n, kGeomTile[geom]);
+    uint32_t* totals = hist + (size_t)kRadix * hist_row_stride(nb);
     const int total_bits = end_bit - begin_bit, passes = (total_bits + 7) / 8, width = (total_bits + passes - 1) / passes;
     for (int bit = begin_bit; bit < end_bit; bit += width) {
         const int nbits = (end_bit - bit) < width ? (end_bit - bit) : width;
-        const uint32_t mask = (1u << nbits) - 1u;
-        if (small) hipLaunchKernelGGL(radix_hist_kernel<kSortRoundsSmall>, dim3(nb), dim3(kSortThreads), 0, s, ki, n, n_dev, bit, mask, nb, hist);
-        else hipLaunchKernelGGL(radix_hist_kernel<kSortRoundsLarge>, dim3(nb), dim3(kSortThreads), 0, s, ki, n, n_dev, bit, mask, nb, hist);
-        hipLaunchKernelGGL(radix_rowscan_kernel, dim3(1u << nbits), dim3(kSortThreads), 0, s, hist, nb, totals);
         const uint32_t* vin = (vals_iota && bit == begin_bit) ? nullptr : vi;   // iota payload: generated by the first pass, never read
-        if (small) hipLaunchKernelGGL(radix_scatter_kernel<kSortRoundsSmall>, dim3(nb), dim3(kSortThreads), 0, s, ki, vin, n, n_dev, bit, mask, nb, hist, totals, ko, vo);
-        else hipLaunchKernelGGL(radix_scatter_kernel<kSortRoundsLarge>, dim3(nb), dim3(kSortThreads), 0, s, ki, vin, n, n_dev, bit, mask, nb, hist, totals, ko, vo);
+        switch (geom) {
+            case kGeom2048:  launch_sort_pass<256, 8>(s, n, n_dev, bit, nbits, nb, hist, totals, ki, vin, ko, vo); break;
+            case kGeom4096:  launch_sort_pass<256, 16>(s, n, n_dev, bit, nbits, nb, hist, totals, ki, vin, ko, vo); break;
+            case kGeom8192:  launch_sort_pass<512, 16>(s, n, n_dev, bit, nbits, nb, hist, totals, ki, vin, ko, vo); break;
+            default:         launch_sort_pass<1024, 16>(s, n, n_dev, bit, nbits, nb, hist, totals, ki, vin, ko, vo); break;
+        }
         uint32_t* t;
         t = ki; ki = ko; ko = t;
         t = vi; vi = vo; vo = t;
@@ -593,6 +688,23 @@ int sort_pairs_u32(hipStream_t s, uint32_t n, const uint32_t* n_dev, int begin_b
     *out_keys = ki;
     *out_vals = vi;
     return GRUT_OK;
+}
+
+int sort_pairs_u32(hipStream_t s, uint32_t n, const uint32_t* n_dev, int begin_bit, int end_bit,
+                   uint32_t* keys, uint32_t* vals, uint32_t* keys_tmp, uint32_t* vals_tmp,
+                   void* scratch, size_t scratch_bytes, uint32_t** out_keys, uint32_t** out_vals, bool vals_iota) {
+    return sort_pairs_impl(s, n, n_dev, begin_bit, end_bit, keys, vals, keys_tmp, vals_tmp, scratch, scratch_bytes, out_keys, out_vals, vals_iota, -1);
+}
+
+// the debug entry's geometry argument: keys per tile, 0 = the host's choice
+int sort_pairs_u32_tiled(hipStream_t s, uint32_t n, const uint32_t* n_dev, int begin_bit, int end_bit,
+                         uint32_t* keys, uint32_t* vals, uint32_t* keys_tmp, uint32_t* vals_tmp, bool vals_iota, uint32_t tile_keys,
+                         void* scratch, size_t scratch_bytes, uint32_t** out_keys, uint32_t** out_vals) {
+    int geom = -1;
+    for (int g = 0; g < kNumSortGeoms; ++g)
+        if (tile_keys == kGeomTile[g]) geom = g;
+    GRUT_REQUIRE(tile_keys == 0 || geom >= 0, "sort: tile_keys must be 0, 2048, 4096, 8192 or 16384");
+    return sort_pairs_impl(s, n, n_dev, begin_bit, end_bit, keys, vals, keys_tmp, vals_tmp, scratch, scratch_bytes, out_keys, out_vals, vals_iota, geom);
 }
 
 }  // namespace grut
@@ -619,6 +731,13 @@ int grut_debug_sort_pairs_u32(void* stream, uint32_t n, const uint32_t* n_dev, i
                               uint32_t** sorted_keys, uint32_t** sorted_values) {
     return grut::sort_pairs_u32(reinterpret_cast<hipStream_t>(stream), n, n_dev, begin_bit, end_bit, keys, values, keys_tmp, values_tmp,
                                 scratch, scratch_bytes, sorted_keys, sorted_values, values_iota != 0);
+}
+
+int grut_debug_sort_pairs_u32_tiled(void* stream, uint32_t n, const uint32_t* n_dev, int begin_bit, int end_bit, uint32_t* keys, uint32_t* values,
+                                    uint32_t* keys_tmp, uint32_t* values_tmp, int values_iota, uint32_t tile_keys, void* scratch, uint64_t scratch_bytes,
+                                    uint32_t** sorted_keys, uint32_t** sorted_values) {
+    return grut::sort_pairs_u32_tiled(reinterpret_cast<hipStream_t>(stream), n, n_dev, begin_bit, end_bit, keys, values, keys_tmp, values_tmp,
+                                      values_iota != 0, tile_keys, scratch, scratch_bytes, sorted_keys, sorted_values);
 }
 
 int grut_debug_scan_gather_u32(void* stream, uint32_t n, const uint32_t* in, const uint32_t* gather, uint32_t* out, void* scratch,

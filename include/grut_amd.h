@@ -303,8 +303,8 @@ int gut_profile_read(GutHandle* handle, float* stage_ms /* [GUT_NUM_STAGES] */);
 
 /* ---- stage-level entry points (parity tests drive each stage alone) ------ */
 /* Stable LSD radix sort of (key,value) pairs on key bits [begin_bit,end_bit). tmp buffers sized n.
- * keys and keys_tmp must be 16-byte aligned (the passes read them 16 bytes at a time); a misaligned pointer is GRUT_ERR_BAD_INPUT and
- * nothing is launched. */
+ * keys, keys_tmp and scratch must be 16-byte aligned (the passes read the keys, and scan the histogram rows in scratch, 16 bytes at a
+ * time); a misaligned pointer is GRUT_ERR_BAD_INPUT and nothing is launched. */
 int grut_sort_pairs_u32(void* stream, uint32_t n, int begin_bit, int end_bit,
                         uint32_t* keys, uint32_t* values,
                         uint32_t* keys_tmp, uint32_t* values_tmp,
@@ -324,6 +324,12 @@ uint64_t grut_scan_scratch_bytes(uint32_t n);
 int grut_debug_sort_pairs_u32(void* stream, uint32_t n, const uint32_t* n_dev, int begin_bit, int end_bit,
                               uint32_t* keys, uint32_t* values, uint32_t* keys_tmp, uint32_t* values_tmp, int values_iota,
                               void* scratch, uint64_t scratch_bytes, uint32_t** sorted_keys, uint32_t** sorted_values);
+/* grut_debug_sort_pairs_u32 with the tile geometry of the three-kernel passes forced: tile_keys = keys per workgroup, one of 2048
+ * (256 threads x 8), 4096 (256 x 16), 8192 (512 x 16), 16384 (1024 x 16); 0 = the library's own choice for n.  Any other value is
+ * GRUT_ERR_BAD_INPUT.  grut_sort_scratch_bytes(n) is enough for every geometry. */
+int grut_debug_sort_pairs_u32_tiled(void* stream, uint32_t n, const uint32_t* n_dev, int begin_bit, int end_bit,
+                                    uint32_t* keys, uint32_t* values, uint32_t* keys_tmp, uint32_t* values_tmp, int values_iota,
+                                    uint32_t tile_keys, void* scratch, uint64_t scratch_bytes, uint32_t** sorted_keys, uint32_t** sorted_values);
 int grut_debug_scan_gather_u32(void* stream, uint32_t n, const uint32_t* in, const uint32_t* gather, uint32_t* out,
                                void* scratch, uint64_t scratch_bytes);
 /* Tile ranges of a 3DGUT frame from its sorted tile keys (16-byte aligned) alone: ranges[t] = [first, last) of the entries whose
