@@ -895,19 +895,27 @@ def test_nht_backward_matches_oracle_on_a_larger_frame(half):
     assert _trimmed_rel_err(gf, rf, 3 * flips) < 1e-3
 
 
-@pytest.mark.parametrize("depth_grad", [False, True])
-def test_nht_pixel_pair_sweeps_equal_the_generic_kernels(depth_grad, monkeypatch):
+@pytest.mark.parametrize("depth_grad,inside", [pytest.param(False, False, id="False"), pytest.param(True, False, id="True"),
+                                               pytest.param(True, True, id="inside-True")])
+def test_nht_pixel_pair_sweeps_equal_the_generic_kernels(depth_grad, inside, monkeypatch):
     """The default feature model (48 = 4 x 12 floats, sincos) runs on the pixel-pair half-tile sweeps (csrc/gut_render_nht.inl: checkpointed
     backward tasks, slot gradients, one 48-lane atomic per entry); every other shape on the generic strip kernels, which the goldens and
     the oracle pin above.  Same frame through both - a dense one, tile lists of several 256-entry segments, so that the backward starts
-    most of its tasks from a checkpoint - must agree: images to 2e-5, gradients to 2e-4 of the largest entry."""
+    most of its tasks from a checkpoint - must agree: images to 2e-5, gradients to 2e-4 of the largest entry.
+    `inside`: the same on a frame rendered from inside the cloud (tests/inside_scenes.py, 300 big particles): canonical intersections close
+    to and behind the ray origins."""
     import torch
-    scene = make_scene(n=30000, width=160, height=96, median_scale=0.06, max_density=0.35)
-    feats = np.random.default_rng(9).uniform(-np.pi / 2, np.pi / 2, size=(30000, 48)).astype(np.float32)
+    if inside:
+        from inside_scenes import make_inside_scene
+        scene = make_inside_scene("pinhole", 96, 64, n_far=3000, n_near=600, n_big=300, seed=3)
+    else:
+        scene = make_scene(n=30000, width=160, height=96, median_scale=0.06, max_density=0.35)
+    n, W, H = len(scene["density12"]), scene["W"], scene["H"]
+    feats = np.random.default_rng(9).uniform(-np.pi / 2, np.pi / 2, size=(n, 48)).astype(np.float32)
     gt = importlib.import_module("3dgrut_amd.gut_tracer")
     rng = np.random.default_rng(10)
-    g_fd = torch.as_tensor(rng.normal(size=(96, 160, 25)).astype(np.float32), device="cuda")
-    g_dist = torch.as_tensor(rng.normal(size=(96, 160, 1)).astype(np.float32), device="cuda")
+    g_fd = torch.as_tensor(rng.normal(size=(H, W, 25)).astype(np.float32), device="cuda")
+    g_dist = torch.as_tensor(rng.normal(size=(H, W, 1)).astype(np.float32), device="cuda")
 
     def run(generic):
         if generic:
@@ -938,21 +946,29 @@ def test_nht_pixel_pair_sweeps_equal_the_generic_kernels(depth_grad, monkeypatch
     assert _trimmed_rel_err(gf_f, gf_g, 3 * nflip) < 2e-4 and float(np.abs(gf_g).max()) > 0
 
 
-@pytest.mark.parametrize("depth_grad,rolling", [(False, False), (True, False), (False, True)])
-def test_quarter_tile_forward_equals_the_half_tile_forward(depth_grad, rolling, monkeypatch):
+@pytest.mark.parametrize("depth_grad,rolling,inside", [pytest.param(False, False, False, id="False-False"), pytest.param(True, False, False, id="True-False"),
+                                                       pytest.param(False, True, False, id="False-True"), pytest.param(True, False, True, id="inside-True-False")])
+def test_quarter_tile_forward_equals_the_half_tile_forward(depth_grad, rolling, inside, monkeypatch):
     """Launches that fit the chip at once (BASELINE configs 1 and 2) run the forward with one pixel per lane, a quarter tile per wave
     (csrc/gut_render.hip: gut_render_fwd_quarter_kernel) - the pair sweep's expressions component by component.  The same dense frame (tile
     lists of many 64-entry segments: most gradient-sweep tasks start from a checkpoint, some from a boundary only ONE quarter of the half
     tile reached alive) through both forwards: images, distances, hit counts and - through the checkpoints - every gradient must be
     bit-identical, with and without a depth gradient.  With per-pixel ray origins (the sweeps' non-uniform-origin form) the two compiled
-    sweeps differ by an ulp per hit (median 1.2e-7 on the image): rounding-level agreement is asserted there."""
+    sweeps differ by an ulp per hit (median 1.2e-7 on the image): rounding-level agreement is asserted there.
+    `inside`: the same equalities on a frame rendered from inside the cloud (tests/inside_scenes.py: 300 big particles, 214 of them on every
+    tile of the 96x64 frame, ray origins inside particles, half of the cloud behind the sensor)."""
     import torch
-    scene = make_scene(n=30000, width=160, height=96, median_scale=0.06, max_density=0.35)
+    if inside:
+        from inside_scenes import make_inside_scene
+        scene = make_inside_scene("pinhole", 96, 64, n_far=3000, n_near=600, n_big=300, seed=3)
+    else:
+        scene = make_scene(n=30000, width=160, height=96, median_scale=0.06, max_density=0.35)
+    W, H = scene["W"], scene["H"]
     rng = np.random.default_rng(12)
     if rolling:   # every pixel its own ray origin (what a moving sensor's rays look like): the sweeps' non-uniform-origin form
         scene["batch"]["rays_ori"] = (scene["batch"]["rays_ori"] + 2e-3 * rng.normal(size=scene["batch"]["rays_ori"].shape)).astype(np.float32)
-    g_fd = rng.normal(size=(96, 160, 4)).astype(np.float32)
-    g_dist = rng.normal(size=(96, 160, 1)).astype(np.float32) if depth_grad else None
+    g_fd = rng.normal(size=(H, W, 4)).astype(np.float32)
+    g_dist = rng.normal(size=(H, W, 1)).astype(np.float32) if depth_grad else None
 
     def run(quarter):
         monkeypatch.setenv("GRUT_FWD_QUARTER", "1" if quarter else "0")
