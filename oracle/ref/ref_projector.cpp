@@ -40,16 +40,42 @@ struct TGUTProjectorParams {
     static constexpr bool BackwardProjection = false;
     static constexpr bool MipSplattingScaling = true;
 };
+// Each value but the last can be overridden on the compiler's command line (-DREF_UT_ALPHA=0.6f ...): libref_projector_utw.so / _utv.so
+// of the Makefile are this file at non-default render.splat settings (tests/golden/projector_ut.npz).  gutProjector.cuh reads every one
+// of them from this block (UTParams::, :150-201), the iteration count as the template argument of projectPointWithShutter (:152-179).
+// REF_UT_DELTA must be given with REF_UT_ALPHA / REF_UT_KAPPA: sqrt(Alpha^2 (D + Kappa)) (setup_3dgut.py:44) is no constant expression.
+#ifndef REF_UT_N_ROLLING_SHUTTER_ITERATIONS
+#define REF_UT_N_ROLLING_SHUTTER_ITERATIONS 5
+#endif
+#ifndef REF_UT_ALPHA
+#define REF_UT_ALPHA 1.0f
+#endif
+#ifndef REF_UT_BETA
+#define REF_UT_BETA 2.0f
+#endif
+#ifndef REF_UT_KAPPA
+#define REF_UT_KAPPA 0.0f
+#endif
+#ifndef REF_UT_DELTA
+#define REF_UT_DELTA 1.7320508075688772f
+#endif
+#ifndef REF_UT_IMAGE_MARGIN_FACTOR
+#define REF_UT_IMAGE_MARGIN_FACTOR 0.1f
+#endif
 struct TGUTProjectionParams {
-    static constexpr int NRollingShutterIterations = 5;
+    static constexpr int NRollingShutterIterations = REF_UT_N_ROLLING_SHUTTER_ITERATIONS;
     static constexpr int D = 3;
-    static constexpr float Alpha = 1.0f;
-    static constexpr float Beta = 2.0f;
-    static constexpr float Kappa = 0.0f;
-    static constexpr float Delta = 1.7320508075688772f;  // sqrt(Alpha^2 (D + Kappa))
-    static constexpr float ImageMarginFactor = 0.1f;
-    static constexpr bool RequireAllSigmaPoints = false;
+    static constexpr float Alpha = REF_UT_ALPHA;
+    static constexpr float Beta = REF_UT_BETA;
+    static constexpr float Kappa = REF_UT_KAPPA;
+    static constexpr float Delta = REF_UT_DELTA;  // sqrt(Alpha^2 (D + Kappa))
+    static constexpr float ImageMarginFactor = REF_UT_IMAGE_MARGIN_FACTOR;
+    static constexpr bool RequireAllSigmaPoints = false;  // threedgut.cuh:79 static_asserts it
 };
+static_assert((TGUTProjectionParams::Delta * TGUTProjectionParams::Delta -
+               TGUTProjectionParams::Alpha * TGUTProjectionParams::Alpha * (TGUTProjectionParams::D + TGUTProjectionParams::Kappa)) < 1e-5f &&
+              (TGUTProjectionParams::Alpha * TGUTProjectionParams::Alpha * (TGUTProjectionParams::D + TGUTProjectionParams::Kappa) -
+               TGUTProjectionParams::Delta * TGUTProjectionParams::Delta) < 1e-5f, "REF_UT_DELTA must be sqrt(Alpha^2 (D + Kappa))");
 
 #include <3dgut/kernels/cuda/renderers/gutProjector.cuh>
 

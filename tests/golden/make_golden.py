@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Generates tests/golden/per_hit_deg{2,4}.npz, gut_hit_seed77.npz, adam.npz, camera.npz, projector.npz, grt_proxies.npz, grt_trace.npz and
+"""Generates tests/golden/per_hit_deg{2,4}.npz, gut_hit_seed77.npz, adam.npz, camera.npz, projector.npz, projector_shutters.npz, projector_ut.npz, grt_proxies.npz, grt_trace.npz and
 gut_render.npz from the REFERENCE's own per-hit math, optimizer kernel, camera projection code, projection stage, 3DGRT
 proxy kernels and OptiX programs, and 3DGUT projection / render / renderBackward kernels.
 
@@ -243,6 +243,9 @@ def make_camera():
     print("wrote camera.npz", sum(int(v.sum()) for k, v in out.items() if "_ok" in k), "valid projections")
 
 
+PROJECTOR_SHUTTERS_N, PROJECTOR_UT_N = 700, 700   # particles per case of projector_shutters.npz / projector_ut.npz
+
+
 def projector_cases(seed=33, n=700):
     """Particle clouds in front of the cameras of camera_cases() (one shutter type per model is enough here: the shutter
     logic itself is pinned by camera.npz): anisotropic scales, random rotations, densities on both sides of 1/255."""
@@ -282,6 +285,97 @@ def make_projector():
         out[f"p{k}_sorted_keys"], out[f"p{k}_sorted_idx"] = keys[order], idx[order]
     np.savez_compressed(os.path.join(HERE, "projector.npz"), **out)
     print("wrote projector.npz:", {k: int((v > 0).sum()) for k, v in out.items() if k.endswith("_tiles")})
+
+
+def _projector_cloud(r, n):
+    """projector_cases()'s cloud recipe, drawn from generator r."""
+    pos = np.concatenate([r.uniform(-2.2, 2.2, (n, 2)), r.uniform(-0.3, 6.0, (n, 1))], 1)
+    scl = np.exp(r.normal(np.log(0.05), 0.8, (n, 3)))
+    q = r.normal(size=(n, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    dens = np.where(r.uniform(size=(n, 1)) < 0.1, r.uniform(0.0, 0.006, (n, 1)), r.uniform(0.01, 1.0, (n, 1)))
+    return np.concatenate([pos, dens, q, scl, np.zeros((n, 1))], 1).astype(F)
+
+
+# One cloud seed per case: the first of its block of a thousand (1000, 2000, ...) for which float32 evaluations on the REFERENCE side
+# support the bounds the GPU test puts on the kernel (tests/test_gut_cameras_cpu.py::test_reference_noise_supports_the_gpu_tests_bounds:
+# no particle whose shutter row, or whose almost-zero off-diagonal conic term, lets two float32 evaluations of it disagree by a good
+# part of a bound).  Nothing about the HIP path enters the condition.
+PROJECTOR_SHUTTER_SEEDS = {(0, 1): 1001, (0, 2): 2005, (0, 3): 3000, (1, 1): 4030, (1, 2): 5005, (1, 3): 6005, (2, 1): 7008, (2, 2): 8008, (2, 3): 9012}
+
+
+def projector_shutter_cases(n=PROJECTOR_SHUTTERS_N):
+    """The nine (model, shutter) pairs of camera_cases() that projector_cases() leaves out: rolling left-to-right, bottom-to-top and
+    right-to-left (shutters 1, 2, 3) for each model - f-theta left-to-right and right-to-left with ANGLE_TO_PIXELDIST as the reference
+    polynomial (prm[17] = shutter % 2).  Clouds by projector_cases()'s recipe, each from a seed of its own."""
+    return [dict(c, d12=_projector_cloud(np.random.default_rng(PROJECTOR_SHUTTER_SEEDS[c["model"], c["shutter"]]), n))
+            for c in camera_cases() if c["shutter"] in (1, 2, 3)]
+
+
+# render.splat of the two further builds of oracle/ref/ref_projector.cpp (oracle/ref/Makefile: libref_projector_ut{w,v}.so) and, per
+# build, the (model, shutter, cloud seed) of the cases they run on: one case per model on a camera of camera_cases(), shutters 1, 2 and 3
+# in each build, f-theta once with ANGLE_TO_PIXELDIST (shutter 3) and once with PIXELDIST_TO_ANGLE (shutter 2).
+# ut_require_all_sigma_points_valid = true has no build: the reference's own configuration header refuses it (threedgut.cuh:79,
+# static_assert), and so does gut_create.
+PROJECTOR_UT_BUILDS = (
+    ("utw", dict(ut_alpha=0.6, ut_beta=1.5, ut_kappa=1.0), ((0, 1, 10001), (1, 2, 11024), (2, 3, 12013))),
+    ("utv", dict(ut_in_image_margin_factor=0.0, n_rolling_shutter_iterations=2), ((0, 3, 13000), (1, 1, 14034), (2, 2, 15004))),
+)
+
+
+def projector_ut_cases(n=PROJECTOR_UT_N):
+    """Six cases for tests/golden/projector_ut.npz: (build name, render.splat keys) of PROJECTOR_UT_BUILDS with a camera of
+    camera_cases() and a cloud by projector_cases()'s recipe each."""
+    cams = {(c["model"], c["shutter"]): c for c in camera_cases()}
+    cases = []
+    for build, splat, triples in PROJECTOR_UT_BUILDS:
+        for model, shutter, seed in triples:
+            cases.append(dict(cams[model, shutter], d12=_projector_cloud(np.random.default_rng(seed), n), build=build, splat=dict(splat)))
+    return cases
+
+
+def _reference_projection(lib, c):
+    """GUTProjector::eval on case c, GUTProjector::expand on its outputs, then the stable sort by key of gutRenderer.cu:356-365 (CUB
+    radix sort): the fields of projector.npz."""
+    n = len(c["d12"])
+    tc = np.zeros(n, np.uint32); pp = np.zeros((n, 2), F); co = np.zeros((n, 4), F); ex = np.zeros((n, 2), F)
+    dp = np.zeros(n, F); vis = np.zeros(n, np.int32)
+    lib.ref_project_particles(c["model"], c["shutter"], c["W"], c["H"], _p(c["prm"]), _p(c["ps"]), _p(c["pe"]), C.c_uint32(n), _p(c["d12"]),
+                              _p(tc), _p(pp), _p(co), _p(ex), _p(dp), _p(vis))
+    offsets = np.cumsum(tc, dtype=np.uint64).astype(np.uint32)
+    total = int(offsets[-1])
+    keys, idx = np.zeros(total, np.uint64), np.zeros(total, np.uint32)
+    lib.ref_expand_particles(c["W"], c["H"], C.c_uint32(n), _p(offsets), _p(pp), _p(co), _p(ex), _p(dp), _p(keys), _p(idx))
+    order = np.argsort(keys, kind="stable")
+    return dict(tiles=tc, pos=pp, conic=co, extent=ex, depth=dp, vis=vis, sorted_keys=keys[order], sorted_idx=idx[order])
+
+
+def make_projector_shutters():
+    """tests/golden/projector_shutters.npz: the fields of projector.npz for projector_shutter_cases(), from the same library
+    (oracle/_ref/libref_projector.so, default render.splat)."""
+    lib = C.CDLL(os.path.join(REF, "libref_projector.so"))
+    out = {}
+    for k, c in enumerate(projector_shutter_cases()):
+        for name, v in _reference_projection(lib, c).items():
+            out[f"p{k}_{name}"] = v
+    np.savez_compressed(os.path.join(HERE, "projector_shutters.npz"), **out)
+    print("wrote projector_shutters.npz:", {k: int((v > 0).sum()) for k, v in out.items() if k.endswith("_tiles")})
+
+
+def make_projector_ut():
+    """tests/golden/projector_ut.npz: the fields of projector.npz for projector_ut_cases(), from oracle/_ref/libref_projector_utw.so
+    (ut_alpha 0.6, ut_beta 1.5, ut_kappa 1, Delta = sqrt(Alpha^2 (3 + Kappa)) = 1.2) and libref_projector_utv.so
+    (ut_in_image_margin_factor 0, n_rolling_shutter_iterations 2).  gutProjector.cuh reads each of these constants from the UTParams block
+    that ref_projector.cpp hands it (:150-201; the iteration count is the template argument of projectPointWithShutter at :152, :168,
+    :179, taken from the same block), so both builds express their settings in full.  RequireAllSigmaPoints = true is the one setting of
+    that block no build has: the reference's threedgut.cuh:79 static_asserts it false."""
+    libs = {b: C.CDLL(os.path.join(REF, f"libref_projector_{b}.so")) for b, _, _ in PROJECTOR_UT_BUILDS}
+    out = {}
+    for k, c in enumerate(projector_ut_cases()):
+        for name, v in _reference_projection(libs[c["build"]], c).items():
+            out[f"p{k}_{name}"] = v
+    np.savez_compressed(os.path.join(HERE, "projector_ut.npz"), **out)
+    print("wrote projector_ut.npz:", {k: int((v > 0).sum()) for k, v in out.items() if k.endswith("_tiles")})
 
 
 def make_grt_proxies():
@@ -1029,7 +1123,7 @@ def make_playground():
 if __name__ == "__main__":
     import sys
     only = [a for a in sys.argv[1:] if a.startswith("--only=")]
-    which = only[0][len("--only="):].split(",") if only else ["per_hit", "adam", "camera", "projector", "grt_proxies", "grt_trace", "grt_trace_mesh", "gut_render", "playground", "gut_nht", "grt_trace_nht", "grt_trace_nht_mesh", "grt_trace_slang_sh", "grt_trace_sphere", "grt_trace_bary", "gut_hit_seed77", "grt_trace_slang_sh_prims"]
+    which = only[0][len("--only="):].split(",") if only else ["per_hit", "adam", "camera", "projector", "projector_shutters", "projector_ut", "grt_proxies", "grt_trace", "grt_trace_mesh", "gut_render", "playground", "gut_nht", "grt_trace_nht", "grt_trace_nht_mesh", "grt_trace_slang_sh", "grt_trace_sphere", "grt_trace_bary", "gut_hit_seed77", "grt_trace_slang_sh_prims"]
     if "--adam-only" in sys.argv:
         which = ["adam"]
     if "per_hit" in which:
@@ -1043,6 +1137,10 @@ if __name__ == "__main__":
         make_camera()
     if "projector" in which:
         make_projector()
+    if "projector_shutters" in which:
+        make_projector_shutters()
+    if "projector_ut" in which:
+        make_projector_ut()
     if "grt_proxies" in which:
         make_grt_proxies()
     if "grt_trace" in which:
