@@ -184,6 +184,7 @@ MCMC_ROLE_COPY, MCMC_ROLE_NEW_DENSITY, MCMC_ROLE_NEW_SCALE, MCMC_ROLE_STATE = ra
 # every symbol include/grut_amd.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = [
     "gut_create", "gut_destroy", "gut_forward", "gut_backward", "gut_backward_unpacked", "gut_forward_split", "gut_backward_split", "gut_backward_unpacked_split", "gut_backward_factored", "gut_backward_factored_chunked", "grut_sph_grad_from_views", "gut_timings", "gut_stats",
+    "gut_forward_only", "gut_forward_only_split", "gut_memory",
     "gut_profile_enable", "gut_profile_select", "gut_profile_read",
     "gut_debug_fetch", "gut_debug_fetch_work", "grut_debug_pose_from_c2w", "grut_debug_frame_poses", "grut_sort_pairs_u32", "grut_sort_scratch_bytes", "grut_inclusive_scan_u32",
     "grut_scan_scratch_bytes", "grut_debug_sort_pairs_u32", "grut_debug_sort_pairs_u32_tiled", "grut_debug_scan_gather_u32", "gut_debug_tile_ranges", "grt_debug_list_ranges",
@@ -235,6 +236,13 @@ def _declare(lib):
     lib.gut_backward_split.restype = C.c_int
     lib.gut_backward_unpacked_split.argtypes = [C.c_void_p, vp, C.POINTER(GutFrame)] + [fp] * 8 + [C.POINTER(GutGradIO), fp, fp]
     lib.gut_backward_unpacked_split.restype = C.c_int
+    # the forward-only twins of the two forwards (same argument lists), and the handle's scratch bytes {all, lists, checkpoint tables}
+    lib.gut_forward_only.argtypes = list(lib.gut_forward.argtypes)
+    lib.gut_forward_only.restype = C.c_int
+    lib.gut_forward_only_split.argtypes = list(lib.gut_forward_split.argtypes)
+    lib.gut_forward_only_split.restype = C.c_int
+    lib.gut_memory.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.gut_memory.restype = C.c_int
     lib.grut_sph_grad_from_views.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, C.c_uint32, C.c_int32, C.c_int32, C.c_float, fp]
     lib.grut_sph_grad_from_views.restype = C.c_int
     lib.gut_timings.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]

@@ -50,6 +50,8 @@ struct GutHandle {
     hipEvent_t count_event = nullptr;
     // forward context consumed by backward (role of GutRenderForwardContext)
     bool have_forward = false;
+    // the last frame came through gut_forward_only*: it wrote no checkpoints, boundary tiles or reached marks, so no backward may follow it
+    bool forward_only = false;
     hipStream_t fwd_stream = nullptr;
     // identity of the forward the context belongs to: the backward must be handed the same frame and the very buffers that
     // forward saw (the packed particle buffer is a fresh allocation per forward that the caller keeps alive until the backward,
@@ -191,6 +193,7 @@ static int ensure_particle_scratch(GutHandle* h, uint32_t N) {
     return GRUT_OK;
 }
 
+// The lists of a frame's tile entries (20 B per entry) and what sorts them; the tables a backward needs on top are ensure_checkpoint_tables'
 static int ensure_intersection_scratch(GutHandle* h, uint32_t I, uint32_t tiles) {
     const size_t n = I ? I : 1;
     if (n > h->tile_capacity) h->tile_capacity = (uint32_t)n;
@@ -201,7 +204,14 @@ static int ensure_intersection_scratch(GutHandle* h, uint32_t I, uint32_t tiles)
     GRUT_CHECK(h->pos_particle.ensure(n * 4, 1.3f));
     GRUT_CHECK(h->tile_sort_scratch.ensure(sort_scratch_bytes((uint32_t)n), 1.3f));
     GRUT_CHECK(h->ranges.ensure((size_t)tiles * 8 + 8));
-    const size_t nb = (size_t)I / kGutSegment + 1;
+    return GRUT_OK;
+}
+
+// The tables a backward needs next to lists of `entries` tile entries (h->tile_capacity: the speculative tail may fill the lists that
+// far).  Training frames only: a forward-only frame (gut_forward_only*) neither allocates nor grows them.  Nothing happens when they
+// are large enough already.
+static int ensure_checkpoint_tables(GutHandle* h, uint32_t entries) {
+    const size_t nb = (size_t)entries / kGutSegment + 1;
     // {T, C} + D per segment boundary, half tile and pixel: 80 B of space per tile entry with 64-entry segments, touched only where a forward
     // wave arrives alive.  Only the unsorted SH sweeps read them: the feature sweeps keep their own table (ck_nht below), the sorted mode
     // and the strip kernels have no checkpoints - those configurations do not pay for the space (several GB at tens of millions of entries)
@@ -272,15 +282,17 @@ int gut_create(const GutConfig* config, GutHandle** handle) {
     return GRUT_OK;
 }
 
-static void release_scratch(GutHandle* h) {
-    DeviceBuffer* bufs[] = {&h->tiles_count, &h->proj_pos, &h->conic_opacity, &h->extent, &h->depth, &h->rgb, &h->depth_key,
+static std::vector<DeviceBuffer*> scratch_buffers(GutHandle* h) {   // every device buffer the handle owns
+    return {&h->tiles_count, &h->proj_pos, &h->conic_opacity, &h->extent, &h->depth, &h->rgb, &h->depth_key,
                             &h->particle_idx, &h->depth_key_tmp, &h->particle_idx_tmp, &h->offsets, &h->sort_scratch,
                             &h->scan_scratch, &h->counters, &h->rec64, &h->walk8, &h->part_offset, &h->pos_particle, &h->grad_partial, &h->grad_flag,
                             &h->grad_touched,
                             &h->g_rgb, &h->poses_dev, &h->work_counters, &h->tile_keys, &h->tile_vals, &h->tile_keys_tmp,
                             &h->tile_vals_tmp, &h->tile_sort_scratch, &h->ranges, &h->ck_tc, &h->ck_d, &h->ck_nht, &h->ck_reached,
                             &h->ck_boundary_tile};
-    for (DeviceBuffer* b : bufs) b->release();
+}
+static void release_scratch(GutHandle* h) {
+    for (DeviceBuffer* b : scratch_buffers(h)) b->release();
 }
 
 // Hand every scratch buffer back (to hipFree or the caller's allocator); the handle stays usable, the next frame allocates afresh.
@@ -292,6 +304,7 @@ int gut_trim(GutHandle* h) {
     release_scratch(h);
     h->tile_capacity = 0;
     h->have_forward = false;
+    h->forward_only = false;
     h->num_intersections = 0;
     h->sorted_pos = nullptr;
     h->sorted_tile_keys = nullptr;
@@ -319,9 +332,11 @@ void gut_destroy(GutHandle* h) {
 }
 
 // gut_forward / gut_forward_split: the SH coefficients are particle_sph, or (split.specular) the model's two tensors
+// gut_forward_only / gut_forward_only_split (forward_only): the same frame without anything a backward would read - the sweeps'
+// builds without checkpoint stores, no boundary-tile table, no reached marks, no checkpoint tables allocated or grown
 static int forward_impl(GutHandle* h, void* stream_, const GutFrame* frame, const float* particle_density, const void* particle_sph_,
                         const GutSplitSph& split, const float* ray_origin, const float* ray_direction, void* out_feat_density_,
-                        float* out_hit_distance, float* out_hit_count, int32_t* out_visibility) {
+                        float* out_hit_distance, float* out_hit_count, int32_t* out_visibility, bool forward_only = false) {
     // (fp32 buffers by default; IEEE half with particle_feature_half / feature_output_half: the kernels look at GutParams::sph_half / out_half)
     const float* particle_sph = reinterpret_cast<const float*>(particle_sph_);
     float* out_feat_density = reinterpret_cast<float*>(out_feat_density_);
@@ -331,6 +346,7 @@ static int forward_impl(GutHandle* h, void* stream_, const GutFrame* frame, cons
     hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
     ScratchStreamScope scratch_scope(s);
     h->have_forward = false;
+    h->forward_only = forward_only;
     const uint32_t N = frame->num_particles;
     h->params = make_params(h->cfg, *frame);
     const GutParams& P = h->params;
@@ -410,8 +426,18 @@ static int forward_impl(GutHandle* h, void* stream_, const GutFrame* frame, cons
     // here, gutRenderer.cu:313-321).  Only if the count turns out to exceed the capacity is the tail redone.
     // the only per-tile buffer: a frame with more tiles than any before must find it large enough for the speculative tail
     GRUT_CHECK(h->ranges.ensure((size_t)tiles * 8 + 8));
+    if (!forward_only && h->tile_capacity > 0) {
+        // a training frame that speculates against lists which forward-only frames sized: the checkpoint tables may be missing or
+        // shorter than those lists.  (Nothing happens when training frames sized them: both come from the same count.)
+        const size_t reached_bytes = h->ck_reached.bytes;
+        GRUT_CHECK(ensure_checkpoint_tables(h, h->tile_capacity));
+        if (h->ck_reached.bytes != reached_bytes) GRUT_HIP(hipMemsetAsync(h->ck_reached.ptr, 0, h->ck_reached.bytes, s));   // new memory: all of it
+    }
+    // (a forward-only frame leaves the reached marks of an earlier training frame as they are: the next training frame clears them here)
+    const GutCheckpoints no_checkpoints = {};
+    const GutCheckpoints& ck = forward_only ? no_checkpoints : h->checkpoints;
     launch_prepare_tail(s, h->offsets.as<uint32_t>() + (N - 1), d_counters + 1, h->host_counters, h->ranges.as<uint32_t>(), tiles * 2u,
-                        h->ck_reached.as<uint32_t>(), h->ck_reached.ptr ? h->ck_boundaries_capacity : 0u);
+                        h->ck_reached.as<uint32_t>(), h->ck_reached.ptr && !forward_only ? h->ck_boundaries_capacity : 0u);
     GRUT_HIP(hipEventRecord(h->count_event, s));
     const uint32_t tile_mask = (h->stats.key_bits >= 32) ? 0xFFFFFFFFu : ((1u << h->stats.key_bits) - 1u);
     bool first_tail = true;
@@ -435,16 +461,16 @@ static int forward_impl(GutHandle* h, void* stream_, const GutFrame* frame, cons
         GRUT_CHECK(h->stage_begin(GUT_STAGE_TILE_RANGES, s, slot));
         if (!first_tail) {   // (the first tail of a frame finds both tables cleared by the tail preparation)
             GRUT_HIP(hipMemsetAsync(h->ranges.ptr, 0, (size_t)tiles * 8, s));
-            GRUT_HIP(hipMemsetAsync(h->ck_reached.ptr, 0, (size_t)h->ck_boundaries_capacity * 4, s));
+            if (!forward_only) GRUT_HIP(hipMemsetAsync(h->ck_reached.ptr, 0, (size_t)h->ck_boundaries_capacity * 4, s));
         }
         first_tail = false;
-        launch_tile_ranges(s, n, n_dev, tile_mask, tiles, sorted_tiles, h->ranges.as<uint32_t>(), h->checkpoints.boundary_tile);
+        launch_tile_ranges(s, n, n_dev, tile_mask, tiles, sorted_tiles, h->ranges.as<uint32_t>(), ck.boundary_tile);
         GRUT_CHECK(h->stage_end(GUT_STAGE_TILE_RANGES, s, slot));
         // K7 compositing
         GRUT_CHECK(h->stage_begin(GUT_STAGE_RENDER_FWD, s, slot));
         if (nht_fast_path(P))
             launch_render_nhtp_fwd(s, P, h->ranges.as<uint32_t>(), sorted_idx, h->pos_particle.as<uint32_t>(), particle_density, particle_sph, ray_origin,
-                                   ray_direction, out_feat_density, out_hit_distance, out_hit_count, h->ck_nht.ptr, h->checkpoints, true);
+                                   ray_direction, out_feat_density, out_hit_distance, out_hit_count, forward_only ? nullptr : h->ck_nht.ptr, ck, !forward_only);
         else if (P.nht)
             launch_render_nht_fwd(s, P, h->ranges.as<uint32_t>(), sorted_idx, h->pos_particle.as<uint32_t>(), particle_density, particle_sph, ray_origin,
                                   ray_direction, out_feat_density, out_hit_distance, out_hit_count);
@@ -453,7 +479,7 @@ static int forward_impl(GutHandle* h, void* stream_, const GutFrame* frame, cons
                                 ray_direction, out_feat_density, out_hit_distance, out_hit_count);
         else
             launch_render_fwd(s, P, h->ranges.as<uint32_t>(), sorted_idx, h->pos_particle.as<uint32_t>(), particle_density, proj.rgb, ray_origin,
-                              ray_direction, out_feat_density, out_hit_distance, out_hit_count, h->checkpoints, true);
+                              ray_direction, out_feat_density, out_hit_distance, out_hit_count, ck, !forward_only);
         GRUT_CHECK(h->stage_end(GUT_STAGE_RENDER_FWD, s, slot));
         return GRUT_OK;
     };
@@ -479,10 +505,11 @@ static int forward_impl(GutHandle* h, void* stream_, const GutFrame* frame, cons
     }
     if (!speculative || I > h->tile_capacity) {
         GRUT_CHECK(ensure_intersection_scratch(h, I + I / 2, tiles));  // head-room: the next frames speculate against it
+        if (!forward_only) GRUT_CHECK(ensure_checkpoint_tables(h, h->tile_capacity));
         first_tail = false;   // (re)allocated tables: clear them explicitly
         GRUT_CHECK(enqueue_tail(I, nullptr));
     }
-    h->checkpoints.num_boundaries = I / kGutSegment + 1;  // what the gradient sweep iterates over
+    if (!forward_only) h->checkpoints.num_boundaries = I / kGutSegment + 1;  // what the gradient sweep iterates over
     GRUT_HIP(hipGetLastError());
     if (h->cfg.enable_kernel_timings) GRUT_CHECK(h->fwd_timer.end(s));
     h->have_forward = true;
@@ -523,6 +550,30 @@ int gut_forward_split(GutHandle* h, void* stream, const GutFrame* frame, const f
                         out_feat_density, out_hit_distance, out_hit_count, out_visibility);
 }
 
+int gut_forward_only(GutHandle* h, void* stream, const GutFrame* frame, const float* particle_density, const void* particle_sph,
+                     const float* ray_origin, const float* ray_direction, void* out_feat_density, float* out_hit_distance,
+                     float* out_hit_count, int32_t* out_visibility) {
+    return forward_impl(h, stream, frame, particle_density, particle_sph, GutSplitSph{}, ray_origin, ray_direction, out_feat_density,
+                        out_hit_distance, out_hit_count, out_visibility, true);
+}
+
+int gut_forward_only_split(GutHandle* h, void* stream, const GutFrame* frame, const float* particle_density, const float* sph_albedo,
+                           const float* sph_specular, const float* ray_origin, const float* ray_direction, void* out_feat_density,
+                           float* out_hit_distance, float* out_hit_count, int32_t* out_visibility) {
+    GRUT_CHECK(split_preconditions(h, "gut_forward_only_split", {sph_albedo, sph_specular}));
+    return forward_impl(h, stream, frame, particle_density, nullptr, GutSplitSph{sph_albedo, sph_specular}, ray_origin, ray_direction,
+                        out_feat_density, out_hit_distance, out_hit_count, out_visibility, true);
+}
+
+int gut_memory(GutHandle* h, uint64_t out[3]) {
+    GRUT_REQUIRE(h && out, "gut_memory: null argument");
+    out[0] = out[1] = out[2] = 0;
+    for (const DeviceBuffer* b : scratch_buffers(h)) out[0] += b->bytes;
+    for (const DeviceBuffer* b : {&h->tile_keys, &h->tile_vals, &h->tile_keys_tmp, &h->tile_vals_tmp, &h->pos_particle}) out[1] += b->bytes;
+    for (const DeviceBuffer* b : {&h->ck_tc, &h->ck_d, &h->ck_reached, &h->ck_boundary_tile, &h->ck_nht}) out[2] += b->bytes;
+    return GRUT_OK;
+}
+
 // The gradient slots of a backward over I tile entries: the partials and both levels of marks (GutGradSlots).  Marks are not cleared per
 // backward - the finalisation leaves them zero - only when their buffer is new (first use, growth, after gut_trim) or the handle is dirty.
 static int prepare_grad_slots(GutHandle* h, hipStream_t s, size_t I, GutGradSlots& slots) {
@@ -551,6 +602,11 @@ static int backward_impl(GutHandle* h, void* stream_, const GutFrame* frame, con
     GRUT_REQUIRE(h && frame, "gut_backward: null handle/frame");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream_);
     ScratchStreamScope scratch_scope(s);
+    if (h->forward_only) {   // before anything is launched or read: that frame left no checkpoints, boundary tiles or reached marks
+        set_last_error("gut_backward: the last frame on this handle was forward-only (gut_forward_only / gut_forward_only_split keep no "
+                       "backward state); render the frame with gut_forward / gut_forward_split to differentiate it");
+        return GRUT_ERR_NOT_READY;
+    }
     if (!h->have_forward || h->fwd_stream != s) {  // gutRenderer.cu:436-440
         set_last_error("gut_backward: no forward context on this stream");
         return GRUT_ERR_NOT_READY;

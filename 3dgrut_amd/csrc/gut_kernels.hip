@@ -734,7 +734,8 @@ __global__ __launch_bounds__(256) void gut_tile_ranges_kernel(uint32_t n_cap, co
         const uint32_t t = key[j] & tile_mask;
         const bool valid = t < num_tiles;
         // segment boundary b sits at sorted index b * kGutSegment; remember which tile's list it cuts
-        if ((k % kGutSegment) == 0) boundary_tile[k / kGutSegment] = valid ? t : 0xFFFFFFFFu;
+        // (boundary_tile == nullptr, a kernel argument and so the same for every lane: a forward-only frame keeps no table)
+        if (boundary_tile && (k % kGutSegment) == 0) boundary_tile[k / kGutSegment] = valid ? t : 0xFFFFFFFFu;
         if (k == 0) {
             if (valid) ranges[t].x = 0;
         } else if (pt != t) {

@@ -56,6 +56,14 @@ def split_sh_requested(conf) -> bool:
     return bool(_conf_get(_conf_get(conf, "render"), "split_sh_features", False)) or bool(os.environ.get("GRUT_SPLIT_SH"))
 
 
+def forward_only_requested(conf) -> bool:
+    """`render.forward_only_inference: true` (a key of this plugin, absent from the reference's configs) or GRUT_FORWARD_ONLY=1: a
+    render() that cannot be differentiated - grad mode off, or no Gaussian tensor of the frame requires grad - takes
+    gut_forward_only / gut_forward_only_split as a plain call: no checkpoint stores, no checkpoint tables, no autograd node.  The
+    reference's 3DGUT plugin has one forward for every frame and ignores `train` (threedgut_tracer/tracer.py:303-349)."""
+    return bool(_conf_get(_conf_get(conf, "render"), "forward_only_inference", False)) or bool(os.environ.get("GRUT_FORWARD_ONLY"))
+
+
 def has_standard_activations(gaussians) -> bool:
     """The model stores raw parameters and activates them with exactly the functions the fused kernels implement
     (threedgrut/model/model.py:237-241 with configs/base_gs.yaml:77-78; utils/misc.py:44-49)."""
@@ -177,7 +185,15 @@ class _GutNative:
         """gut_forward_split: the coefficients as the model's two tensors, [N,3] and [N,45], read where they lie."""
         return self._trace(frame, particle_density, (sph_albedo, sph_specular), ray_ori, ray_dir)
 
-    def _trace(self, frame, particle_density, sph, ray_ori, ray_dir):
+    def trace_forward_only(self, frame, particle_density, particle_sph, ray_ori, ray_dir):
+        """gut_forward_only: trace() for a frame no backward follows (the handle refuses one)."""
+        return self._trace(frame, particle_density, (particle_sph,), ray_ori, ray_dir, forward_only=True)
+
+    def trace_split_forward_only(self, frame, particle_density, sph_albedo, sph_specular, ray_ori, ray_dir):
+        """gut_forward_only_split: trace_split() for a frame no backward follows."""
+        return self._trace(frame, particle_density, (sph_albedo, sph_specular), ray_ori, ray_dir, forward_only=True)
+
+    def _trace(self, frame, particle_density, sph, ray_ori, ray_dir, forward_only=False):
         dev = ray_ori.device
         H, W = frame.height, frame.width
         N = frame.num_particles
@@ -205,7 +221,8 @@ class _GutNative:
         else:
             out_feat, out_opa = _uninitialised((H, W, 3), **opts), _uninitialised((H, W, 1), **opts)
         frame.out_features, frame.out_opacity = (None, None) if half_out else (out_feat.data_ptr(), out_opa.data_ptr())
-        fn, name = (self.lib.gut_forward, "gut_forward") if len(sph) == 1 else (self.lib.gut_forward_split, "gut_forward_split")
+        name = ("gut_forward_only" if forward_only else "gut_forward") + ("" if len(sph) == 1 else "_split")
+        fn = getattr(self.lib, name)
         _abi.check(fn(self.handle, _stream_ptr(dev), C.byref(frame), _ptr(particle_density), *map(_ptr, sph),
                       _ptr(ray_ori), _ptr(ray_dir), _ptr(out_fd), _ptr(out_dist), _ptr(out_cnt), _ptr(vis_i32)), name)
         # the reference returns a float tensor holding the int bit pattern (splatRaster.cpp:215,249); consumers call .bool()
@@ -219,7 +236,11 @@ class _GutNative:
     def ray_feature_dim(self):
         return ray_feature_dim_of(self.cfg)
 
-    def trace_nht(self, frame, particle_density, particle_features, ray_ori, ray_dir):
+    def trace_nht_forward_only(self, frame, particle_density, particle_features, ray_ori, ray_dir):
+        """gut_forward_only of the nht configuration: trace_nht() for a frame no backward follows."""
+        return self.trace_nht(frame, particle_density, particle_features, ray_ori, ray_dir, forward_only=True)
+
+    def trace_nht(self, frame, particle_density, particle_features, ray_ori, ray_dir, forward_only=False):
         """Forward of the neural-harmonic-features configuration (GutConfig::feature_transform_type 1): [H,W,ray_dim+1] features + opacity."""
         dev = ray_ori.device
         H, W, N = frame.height, frame.width, frame.num_particles
@@ -230,8 +251,9 @@ class _GutNative:
         vis = torch.zeros((N, 1), dtype=torch.int32, device=dev)
         if self.cfg.particle_feature_half and particle_features.dtype != torch.float16:
             particle_features = particle_features.to(torch.float16)
-        _abi.check(self.lib.gut_forward(self.handle, _stream_ptr(dev), C.byref(frame), _ptr(particle_density), _ptr(particle_features.contiguous()),
-                                        _ptr(ray_ori), _ptr(ray_dir), _ptr(fd), _ptr(dist), _ptr(cnt), _ptr(vis)), "gut_forward")
+        fn, name = (self.lib.gut_forward_only, "gut_forward_only") if forward_only else (self.lib.gut_forward, "gut_forward")
+        _abi.check(fn(self.handle, _stream_ptr(dev), C.byref(frame), _ptr(particle_density), _ptr(particle_features.contiguous()),
+                      _ptr(ray_ori), _ptr(ray_dir), _ptr(fd), _ptr(dist), _ptr(cnt), _ptr(vis)), name)
         return fd, dist, cnt, vis.view(torch.float32), particle_features
 
     def trace_bwd_nht(self, frame, particle_density, particle_features, ray_ori, ray_dir, fd, g_fd, dist, g_dist):
@@ -334,6 +356,12 @@ class _GutNative:
     def trim(self):
         """gut_trim: hand all scratch back to the allocator (torch's pool by default); the next frame allocates afresh."""
         _abi.check(self.lib.gut_trim(self.handle), "gut_trim")
+
+    def memory(self):
+        """gut_memory: bytes of scratch the handle owns - (all of it, the per-intersection lists, the backward's checkpoint tables)."""
+        out = (C.c_uint64 * 3)()
+        _abi.check(self.lib.gut_memory(self.handle, out), "gut_memory")
+        return tuple(int(v) for v in out)
 
     def stats(self) -> _abi.GutStats:
         s = _abi.GutStats()
@@ -501,6 +529,9 @@ class Tracer:
         self._split_sh = split_sh_requested(conf)
         # which SH path the render() calls took: the two leaves in place, or get_features() (the model's torch.cat)
         self.stats_split = {"split_calls": 0, "cat_calls": 0}
+        self._forward_only = forward_only_requested(conf)
+        # which forward the render() calls took: gut_forward_only* as a plain call, or the autograd Function over gut_forward*
+        self.stats_forward_only = {"forward_only_calls": 0, "training_calls": 0}
         # set to a 3dgrut_amd.dp.FactoredGradientExchange to have the backward exchange its gradients across ranks (one view
         # per GPU); None (default) = single-GPU behaviour, exactly the reference's
         self.gradient_exchange = None
@@ -535,6 +566,57 @@ class Tracer:
                 return None
         return albedo, specular
 
+    def _render_forward_only(self, gaussians, native, frame, rays_o, rays_d, split):
+        """render() for a frame that cannot be differentiated (forward_only_requested): the output dict, or None when the frame can be -
+        grad mode is on and one of the Gaussian tensors it would hand to the autograd Function requires grad.  `train` decides nothing:
+        the reference's 3DGUT ignores it (threedgut_tracer/tracer.py:303-349)."""
+        grad_mode = torch.is_grad_enabled()
+        nht = bool(native.cfg.feature_transform_type)
+        raw = not nht and self._fused_activations and has_standard_activations(gaussians)
+        # the tensors that are the model's own first: a training step is recognised before any activation or torch.cat is evaluated
+        # (only a model whose positions and in-place tensors are all frozen while an activated one still requires grad pays for
+        # evaluating those twice, here and in the path taken instead)
+        held = (gaussians.positions,) + (tuple(split) if split is not None else ()) + ((gaussians.rotation, gaussians.scale, gaussians.density) if raw else ())
+        if grad_mode and any(t.requires_grad for t in held):
+            return None
+        rot, scl, dns = held[-3:] if raw else (gaussians.get_rotation(), gaussians.get_scale(), gaussians.get_density())
+        sph = split if split is not None else (gaussians.get_features(),)
+        if grad_mode and any(t.requires_grad for t in (rot, scl, dns, *sph)):
+            return None
+        if getattr(gaussians, "ray_feature_dim", 3) != 3 and not nht:
+            raise NotImplementedError("3dgrut_amd: only SH radiance features (ray_feature_dim = 3) are supported")
+        self.stats_forward_only["forward_only_calls"] += 1
+        self.stats_split["cat_calls" if split is None else "split_calls"] += 1
+        with torch.no_grad():
+            ro, rd = rays_o.contiguous().float(), rays_d.contiguous().float()
+            pack = _abi.activate_pack if raw else _abi.pack_particles   # (the packing kernels themselves: there is no autograd wrapper here)
+            particle_density = pack(gaussians.positions.contiguous(), dns.contiguous(), rot.contiguous(), scl.contiguous())
+            if split is not None:
+                _, dist, cnt, vis, feat, opa = native.trace_split_forward_only(frame, particle_density, split[0], split[1], ro, rd)
+            elif nht:
+                feats = sph[0]
+                if feats.shape[1] != native.cfg.particle_feature_dim:
+                    raise ValueError(f"features have {feats.shape[1]} columns, expected nht_features.dim = {native.cfg.particle_feature_dim}")
+                fd, dist, cnt, vis, _ = native.trace_nht_forward_only(frame, particle_density, feats.contiguous(), ro, rd)
+                nr = native.ray_feature_dim
+                f32 = fd.float()
+                feat, opa = f32[..., :nr].contiguous(), f32[..., nr:].contiguous()
+            else:
+                feats = sph[0]
+                if feats.shape[1] != 3 * native.ncoef:
+                    raise ValueError(f"features have {feats.shape[1]} columns, expected {3 * native.ncoef} for SH degree "
+                                     f"{native.cfg.particle_radiance_sph_degree}")
+                feats = feats.contiguous()
+                if native.cfg.particle_feature_half and feats.dtype != torch.float16:
+                    feats = feats.to(torch.float16)
+                _, dist, cnt, vis, feat, opa = native.trace_forward_only(frame, particle_density, feats, ro, rd)
+            pred_features, pred_opacity = feat.unsqueeze(0), opa.unsqueeze(0)
+            normals = (torch.nn.functional.normalize(torch.ones_like(pred_features), dim=3) if nht else self._constant_normals(pred_features))
+        timings = native.collect_times()
+        return {"pred_features": pred_features, "pred_opacity": pred_opacity, "pred_dist": dist.unsqueeze(0),
+                "pred_normals": normals, "hits_count": cnt.unsqueeze(0),
+                "frame_time_ms": timings["forward_render"] if "forward_render" in timings else 0.0, "mog_visibility": vis}
+
     def render(self, gaussians, gpu_batch, train=False, frame_id=0):
         rays_o = gpu_batch.rays_ori if not isinstance(gpu_batch, dict) else gpu_batch["rays_ori"]
         rays_d = gpu_batch.rays_dir if not isinstance(gpu_batch, dict) else gpu_batch["rays_dir"]
@@ -553,6 +635,11 @@ class Tracer:
             frame.device_T_to_world_end = None if t1 is None else t1.data_ptr()
             frame._keepalive = (t0, t1)
         split = self._split_sh_tensors(gaussians, rays_o.device)
+        if self._forward_only:
+            out = self._render_forward_only(gaussians, native, frame, rays_o, rays_d, split)
+            if out is not None:
+                return out
+        self.stats_forward_only["training_calls"] += 1
         if split is not None:   # the model's two SH tensors in place: get_features() (model.py:94-96) is not called at all
             if getattr(gaussians, "ray_feature_dim", 3) != 3:
                 raise NotImplementedError("3dgrut_amd: only SH radiance features (ray_feature_dim = 3) are supported")

@@ -244,6 +244,41 @@ int gut_backward_unpacked_split(GutHandle* handle, void* stream, const GutFrame*
                                 const void* feat_density, const float* hit_distance, const float* grad_hit_distance,
                                 const GutGradIO* io, float* grad_sph_albedo, float* grad_sph_specular);
 
+/* ---- frames nobody differentiates (new surface) ----------------------------------------------------------------------------------
+ * gut_forward keeps, next to the image, what gut_backward restarts from: the running state of every pixel at every 64th entry of its
+ * tile's list (80 B of table per tile entry against the 20 B of the lists themselves, plus a table of its own for the neural-harmonic
+ * fast path), the tile each such boundary cuts and the marks of the boundaries a wave reached alive.  Validation passes, rendering,
+ * viewers and visibility filters never run a backward.  gut_forward_only and gut_forward_only_split are gut_forward and
+ * gut_forward_split for those frames (they replace the same SplatRaster::trace, src/splatRaster.cpp:184-261, which has no such mode:
+ * the reference's GUTRenderer fills one forward context for every frame, train or not, gutRenderer.cu:252-253); same arguments, same
+ * preconditions and errors, the same arithmetic in the same order, so every output - image, out_features / out_opacity, hit distance,
+ * hit count, visibility, the N == 0 and no-intersection outputs, gut_stats, gut_timings, gut_debug_fetch - equals the twin's bit for
+ * bit.  What differs:
+ *   - the compositing sweeps run in their builds without checkpoint stores (unsorted SH half-tile and quarter-tile kernels, the
+ *     neural-harmonic fast path; the sorted k-buffer and generic feature forwards never had any), the tile-range pass writes no
+ *     boundary tiles, the reached marks are not cleared;
+ *   - the checkpoint tables are neither allocated nor grown: a handle that only renders such frames never owns them (gut_memory);
+ *   - the handle remembers that its last frame was forward-only, and every gut_backward* entry point then returns
+ *     GRUT_ERR_NOT_READY before anything is launched or read, with a grut_last_error() that says so.  The next gut_forward /
+ *     gut_forward_split clears the mark; it allocates the tables it finds missing or shorter than the lists and starts from cleared
+ *     reached marks, so training and forward-only frames may alternate on one handle in any order, with gut_trim in between or not;
+ *   - an instrumented frame (gut_profile_enable level 2) counts no forward-sweep entries: the counting build is the training sweep's. */
+int gut_forward_only(GutHandle* handle, void* stream, const GutFrame* frame,
+                     const float* particle_density, const void* particle_sph,
+                     const float* ray_origin, const float* ray_direction,
+                     void* out_feat_density, float* out_hit_distance,
+                     float* out_hit_count, int32_t* out_visibility);
+int gut_forward_only_split(GutHandle* handle, void* stream, const GutFrame* frame,
+                           const float* particle_density, const float* sph_albedo, const float* sph_specular,
+                           const float* ray_origin, const float* ray_direction,
+                           void* out_feat_density, float* out_hit_distance,
+                           float* out_hit_count, int32_t* out_visibility);
+/* Bytes of device scratch the handle owns right now (HOST function, no device work; new surface, the reference's
+ * GutRenderForwardContext, gutRenderer.cu:99-110, reports nothing of the kind): out[0] = all of it, out[1] = the five per-intersection lists (tile keys
+ * and payloads with their sort ping-pong, entry -> particle), out[2] = the checkpoint tables of the backward (per-pixel state, its
+ * neural-harmonic twin, reached marks, boundary tiles).  out[2] is 0 for a handle that has only rendered forward-only frames. */
+int gut_memory(GutHandle* handle, uint64_t out[3]);
+
 /* ---- view-sharded data parallelism: the radiance gradient in factored form (new surface; the reference is
  * single-GPU) ------------------------------------------------------------------------------------------------------------------
  * With one view per GPU, the gradient exchange of a step is dominated by grad_particle_sph: 3*(deg+1)^2 floats per particle
